@@ -11,6 +11,11 @@ host from one seed and sliced per rank (weak scaling: B per GPU); no per-step
 collective; one RCCL all_gather_into_tensor of the decoded images at the end of
 every step.  Timing: barrier + synchronize on both sides of the K timed steps,
 max over ranks.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, config).
+--dump-outputs DIR also writes the images of the last timed step to DIR/<name>.npy.  --full adds what
+takes runs of its own after the timed steps: the UNet step latency, the per-kernel / roofline pass and
+the CPU baseline.
 """
 from __future__ import annotations
 
@@ -208,6 +213,25 @@ def rank_inputs(seed, world, rank, batch, latent_shape, ctx_shape, device):
     return xT, ctx
 
 
+DUMP_BYTES = 63 * 1000 * 1000      # budget (under 64 MB with the .npy headers) of one --dump-outputs directory, all arrays together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the arrays the timed path returned in its last step as ``path/<name>.npy``, float32.
+    The arrays share DUMP_BYTES evenly; one that is over its share is written as a fixed sample of its
+    flattened elements (ascending indices drawn without replacement from numpy's default_rng(0)), so two
+    runs with the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // (4 * max(len(arrays), 1))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 # The reference itself timed as written on the survey container's CPU (BASELINE.md:22-25; SURVEY §6):
 # not re-run here (/root/reference does not exist on the GPU box), carried beside the port's figure
 REFERENCE_AS_WRITTEN = {
@@ -289,7 +313,9 @@ def main_ddpm(args, cfg, world, rank, local, dist, device):
                       "image": [3, S, S], "timesteps": T, "parallelism": f"dp{world}", "collective": None},
            "finite": bool(torch.isfinite(img).all().item()), "hip_graph": not args.no_graph,
            "tuning_cache_entries": cached}
-    if not args.no_roofline and rank == 0:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"images": img})
+    if args.full and not args.no_roofline and rank == 0:
         ops.PROFILER.start()
         pipe.sampling(m, x0, device, noise_fn=noise_fn)
         torch.cuda.synchronize()
@@ -306,7 +332,7 @@ def main_ddpm(args, cfg, world, rank, local, dist, device):
                                "frac": round(ach / PEAK_F16_TFLOPS, 4), "traffic": None,
                                "kernel": "conv family (launch-bound at 32x32, B=4)", "launches": conv["launches"],
                                "avg_launch_us": round(1000 * conv["ms"] / conv["launches"], 2)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
         from oracle.ddpm_ref import unet_forward
         torch.set_num_threads(args.cpu_threads)
@@ -451,6 +477,12 @@ def make_parser():
                     help="conv tile/split-K table measured on MI355X (loaded if present; missing problems are timed)")
     ap.add_argument("--tuning-out", default=None, help="write the (extended) tuning table here")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of one HIP graph per UNet step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the UNet step "
+                         "latency, the per-kernel / roofline pass (BENCH_SHAPES_OUT, BENCH_SEQ_OUT) and the CPU "
+                         "baseline (--no-roofline / --no-cpu-baseline drop one of them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (this rank's decoded images) to DIR/<name>.npy")
     return ap
 
 
@@ -496,24 +528,30 @@ def main():
     img, elapsed = timed_steps(one_step, args.steps, max(args.warmup - 1, 0), barrier, device, gtimer)
     finite = bool(torch.isfinite(img).all().item())
     dp = dp_report(img, gathered, rank, world, device, gtimer) if dist else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"gathered_images": gathered} if dist else {"images": img})
 
-    # UNet step latency at the config batch (HIP events around replays of the sampler's UNet call,
-    # through apply_model -> DiffusionWrapper -> graph replay)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    tts = torch.full((B,), 501, dtype=torch.long, device=device)
-    model.apply_model(xT, tts, ctx)
-    torch.cuda.synchronize()
-    e0.record()
-    nrep = 5
-    for _ in range(nrep):
+    # everything below the timed steps is --full only: a plain run goes straight to the result line
+    roofline = args.full and not args.no_roofline and rank == 0
+    unet_ms = None
+    if args.full:
+        # UNet step latency at the config batch (HIP events around replays of the sampler's UNet call,
+        # through apply_model -> DiffusionWrapper -> graph replay)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        tts = torch.full((B,), 501, dtype=torch.long, device=device)
         model.apply_model(xT, tts, ctx)
-    e1.record()
-    torch.cuda.synchronize()
-    unet_ms = e0.elapsed_time(e1) / nrep
+        torch.cuda.synchronize()
+        e0.record()
+        nrep = 5
+        for _ in range(nrep):
+            model.apply_model(xT, tts, ctx)
+        e1.record()
+        torch.cuda.synchronize()
+        unet_ms = e0.elapsed_time(e1) / nrep
 
     # per-kernel breakdown: one extra, untimed, eager step on rank 0 with HIP events
     # around every launch (not part of `value`)
-    if not args.no_roofline and rank == 0:
+    if roofline:
         model.use_graphs(False)
         ops.PROFILER.start()
         z, _ = sampler.sample(S=args.ddim_steps, batch_size=B, shape=(4, L, L), conditioning=ctx, eta=0.0, x_T=xT,
@@ -534,11 +572,13 @@ def main():
                       "parallelism": f"dp{world}", "collective": "all_gather decoded images (RCCL)" if dist else None,
                       "entry": "LatentDiffusion (configs/sd-v1-txt2img.yaml) -> DDIMSampler.sample -> "
                                "decode_first_stage"},
-           "unet_step_ms": round(unet_ms, 3), "finite": finite, "hip_graph": not args.no_graph,
+           "finite": finite, "hip_graph": not args.no_graph,
            "autotuned_conv_problems": len(ops.AUTOTUNE.table), "tuning_cache_entries": cached}
+    if unet_ms is not None:
+        out["unet_step_ms"] = round(unet_ms, 3)
     if dp is not None:
         out.update(dp)
-    if not args.no_roofline and rank == 0:
+    if roofline:
         summ = ops.PROFILER.summary()
         conv = {"launches": 0, "ms": 0.0, "flops": 0.0, "bytes": 0.0}
         for k, d in summ.items():
@@ -596,7 +636,7 @@ def main():
                     f.write(f"{kind:10s} {str(shape):44s} launches={n:5d} ms={ms:9.2f} TFLOP/s={tf:7.1f}\n")
         tot_tf = (unet_gflops_per_image(args.config) * args.ddim_steps + vae_gflops_per_image(args.config)) / 1000
         out["end_to_end_tflops"] = round(tot_tf * value, 1)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.config, cfg, args.ddim_steps, args.cpu_threads)
         if args.config in REFERENCE_AS_WRITTEN:
             out["cpu_baseline"]["reference_as_written"] = REFERENCE_AS_WRITTEN[args.config]

@@ -109,6 +109,26 @@ def test_bench_dp_step_matches_single_process():
     assert dp_bad["gather_slices_bitwise_equal"] is False and dp_bad["gather_mismatched_ranks"] == 1
 
 
+def test_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: an array within the budget is written whole as float32; a larger one as the same
+    seeded sample of its elements on every call; --full and --dump-outputs parse, both off by default."""
+    import bench
+    a = bench.make_parser().parse_args([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.make_parser().parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    img = torch.arange(2 * 3 * 8 * 8, dtype=torch.float16).reshape(2, 3, 8, 8)
+    bench.dump_outputs(str(tmp_path / "a"), {"images": img})
+    got = np.load(tmp_path / "a" / "images.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 100)
+    bench.dump_outputs(str(tmp_path / "b"), {"images": img})
+    bench.dump_outputs(str(tmp_path / "c"), {"images": img})
+    s1, s2 = np.load(tmp_path / "b" / "images.npy"), np.load(tmp_path / "c" / "images.npy")
+    assert s1.dtype == np.float32 and s1.shape == (100,) and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) > 0)                  # distinct elements of the arange, ascending indices
+
+
 def _run_bench(args, env_extra=None):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)

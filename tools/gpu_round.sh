@@ -32,14 +32,14 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   step tests 1100 python -u -m pytest tests -m gpu -v -s --timeout 400 --timeout-method thread
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-  step bench_c3 600 env BENCH_SHAPES_OUT=$O/shapes.txt python -u bench.py --steps 5 --warmup 2
-  step bench_c5 600 python -u bench.py --config c5 --steps 2 --warmup 1
-  step bench_c2 600 python -u bench.py --config c2 --steps 3 --warmup 1
-  step bench_c1 600 python -u bench.py --config c1 --steps 5 --warmup 2
+  step bench_c3 600 env BENCH_SHAPES_OUT=$O/shapes.txt python -u bench.py --full --steps 5 --warmup 2
+  step bench_c5 600 python -u bench.py --full --config c5 --steps 2 --warmup 1
+  step bench_c2 600 python -u bench.py --full --config c2 --steps 3 --warmup 1
+  step bench_c1 600 python -u bench.py --full --config c1 --steps 5 --warmup 2
 fi
 if [ "${SKIP_PROF:-0}" != "1" ]; then
   cd /tmp
-  step trace 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline
+  step trace 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
   step pmc_fetch 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o run -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-roofline --no-graph
   step pmc_write 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o run -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-roofline --no-graph
 fi

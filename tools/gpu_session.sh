@@ -37,12 +37,12 @@ for s in "$@"; do
     ff)      step ff 300 python -u -m pytest tests/test_gpu_ff.py -x -v -s --timeout 120 --timeout-method thread
              step ff_bench 200 python -u tools/bench_ff.py ;;
     tests)   step tests 1100 python -u -m pytest tests -m gpu -v -s --timeout 400 --timeout-method thread ;;
-    bench_c3) step bench_c3 600 env BENCH_SHAPES_OUT=$O/shapes.txt python -u bench.py --steps 5 --warmup 2 ;;
-    bench_c5) step bench_c5 600 python -u bench.py --config c5 --steps 2 --warmup 1 ;;
-    bench_c2) step bench_c2 600 python -u bench.py --config c2 --steps 3 --warmup 1 ;;
-    bench_c1) step bench_c1 600 python -u bench.py --config c1 --steps 5 --warmup 2 ;;
+    bench_c3) step bench_c3 600 env BENCH_SHAPES_OUT=$O/shapes.txt python -u bench.py --full --steps 5 --warmup 2 ;;
+    bench_c5) step bench_c5 600 python -u bench.py --full --config c5 --steps 2 --warmup 1 ;;
+    bench_c2) step bench_c2 600 python -u bench.py --full --config c2 --steps 3 --warmup 1 ;;
+    bench_c1) step bench_c1 600 python -u bench.py --full --config c1 --steps 5 --warmup 2 ;;
     trace)   ( cd /tmp && step trace 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run \
-               -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline ) || exit 1 ;;
+               -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline ) || exit 1 ;;
     pmc_fetch) ( cd /tmp && step pmc_fetch 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o run \
                -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-roofline --no-graph ) || exit 1 ;;
     pmc_write) ( cd /tmp && step pmc_write 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o run \

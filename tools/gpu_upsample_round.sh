@@ -12,6 +12,6 @@ for c in c3 c5 c2; do
 done
 for r in 1 2; do
   for f in 1 0; do
-    SD_AMD_UPSAMPLE_FOLD=$f timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --tuning-cache $T 2>&1 | grep '^{' | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('fold=$f', d['value'], d['unet_step_ms'])" || exit 1
+    SD_AMD_UPSAMPLE_FOLD=$f timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --tuning-cache $T 2>&1 | grep '^{' | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('fold=$f', d['value'], d['unet_step_ms'])" || exit 1
   done
 done
