@@ -353,6 +353,41 @@ typedef struct {
 
 int sdk_ddim_step(const sdk_ddim_args* a, sdk_stream_t stream);
 
+/* Second half of the DDIM update for quantize_denoised (DDIM/ddim.py:196-203): the reference
+ * quantises pred_x0 between the two halves, so here a->pred_x0 is an INPUT and only
+ * x_prev = sqrt_a_prev*pred_x0 + dir_coef*e + sigma*noise*temperature is written (e after the same
+ * guidance combine / v conversion as sdk_ddim_step; x is read only when v_param).  Same operations in
+ * the same order as sdk_ddim_step: fed that call's pred_x0 it reproduces its x_prev bit for bit. */
+int sdk_ddim_xprev(const sdk_ddim_args* a, sdk_stream_t stream);
+
+/* ---------------------------------------------------------------- vector quantiser (vqvae/quantize.py)
+ * norms[j] = |codebook[j]|^2 (fp32 fma chain), computed once per codebook [n][d]. */
+int sdk_vq_code_norms(const float* codebook, float* norms, int32_t n, int32_t d, sdk_stream_t stream);
+
+/* Number of codebook splits sdk_vq_nearest uses for m rows (0: unsupported shape).  With more than
+ * one split the call needs `keys`: 8 bytes per row. */
+int32_t sdk_vq_nearest_splits(int64_t m, int32_t n, int32_t d);
+
+/* Nearest code per row of z (VectorQuantize2.forward, vqvae/quantize.py:131-163) without the [M, n]
+ * distance matrix.  z, z_q: NCHW fp32 [batch][d][hw], read / written in place (row m = (b, pixel));
+ * codebook [n][d] fp32; norms from sdk_vq_code_norms.  idx[m] = argmin_j |e_j|^2 - 2 z_m.e_j in fp32,
+ * the lowest index among equal scores; z_q = z + (e[idx] - z), two roundings.  1 <= d <= 256.
+ * force_splits > 0 overrides the split count (tests); keys may be NULL when one split is used. */
+int sdk_vq_nearest(const float* z, const float* codebook, const float* norms, int64_t* idx, float* z_q,
+                   int32_t batch, int32_t d, int32_t hw, int32_t n, void* keys, int64_t keys_bytes,
+                   int32_t force_splits, sdk_stream_t stream);
+
+/* out = codebook[idx] for m indices: [m][d] (nchw = 0) or [m / hw][d][hw] (nchw = 1)
+ * (get_codebook_entry, ldm/tamming/quantize.py:314-329).  The caller range-checks idx on the host. */
+int sdk_vq_lookup(const int64_t* idx, const float* codebook, float* out, int64_t m, int32_t n, int32_t d,
+                  int32_t hw, int32_t nchw, sdk_stream_t stream);
+
+/* Index remap (vqvae/quantize.py:67-101, ldm/tamming/quantize.py:261-269).  mode 0, remap_to_used:
+ * first position in used[n_used] equal to the index, else rnd[i] (when rnd != NULL) or `unknown`.
+ * mode 1, unmap_to_all: used[index]; with `extra` an index >= n_used is first set to 0. */
+int sdk_vq_remap(const int64_t* inds, const int64_t* used, const int64_t* rnd, int64_t* out, int64_t count,
+                 int32_t n_used, int32_t mode, int64_t unknown, int32_t extra, sdk_stream_t stream);
+
 /* DDPM ancestral update (DDPM/ddpm.py:84-86):
  * x = inv_sqrt_alpha*(x - coef*eps) + sigma*noise. */
 int sdk_ddpm_step(const float* x, const float* eps, const float* noise, float* out, int64_t n,

@@ -7,6 +7,11 @@ update, fp32, no contraction → bit-identical to the reference expression on
 the same inputs).  Per-step scalars are the fp32 values ``torch.full(...)``
 would hold (``ddim.py:189-192``), derived with torch's CPU fp32 ops.
 
+``quantize_x0`` / ``quantize_denoised`` (``ddim.py:196-197``) run step → fused nearest-code search
+on ``pred_x0`` (``first_stage_model.quantize``) → ``sdk_ddim_xprev`` with the quantised value; ``decode``
+takes the flag as well (extension).  Masking, ``score_corrector``, ``noise_dropout`` and original-steps
+stay NotImplementedError.
+
 Extensions (documented, not in the reference): ``parameterization == "v"``
 on the model and an optional ``noise_fn(i, shape)`` hook
 so η>0 runs can be reproduced bit-for-bit.
@@ -85,10 +90,11 @@ class DDIMSampler(object):
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, noise_fn=None):
-        if ddim_use_original_steps or mask is not None or quantize_denoised or score_corrector is not None \
-                or noise_dropout > 0:
-            raise NotImplementedError("sd_amd: original-steps / masking / quantize / score_corrector / "
-                                      "noise_dropout are not on the txt2img hot path")
+        if ddim_use_original_steps or mask is not None or score_corrector is not None or noise_dropout > 0:
+            raise NotImplementedError("sd_amd: original-steps / masking / score_corrector / noise_dropout are "
+                                      "not implemented by this sampler")
+        if quantize_denoised:
+            self._quantizer()
         device = self.model.device
         b = shape[0]
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
@@ -102,6 +108,7 @@ class DDIMSampler(object):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature,
+                                              quantize_denoised=quantize_denoised,
                                               unconditional_guidance_scale=unconditional_guidance_scale,
                                               unconditional_conditioning=unconditional_conditioning,
                                               noise=(noise_fn(i, img.shape) if noise_fn is not None else None))
@@ -126,6 +133,14 @@ class DDIMSampler(object):
         self._cfg_cache = (uc, c, (uc._version, c._version), c_in)
         return c_in
 
+    def _quantizer(self):
+        """The first stage's quantiser for ``quantize_denoised`` (``ddim.py:196-197``), or a clear error."""
+        q = getattr(getattr(self.model, "first_stage_model", None), "quantize", None)
+        if q is None or not hasattr(q, "nearest"):
+            raise AttributeError("sd_amd.DDIMSampler: quantize_x0 / quantize_denoised needs a VQ first stage "
+                                 "(model.first_stage_model.quantize); this model's first stage has no quantizer")
+        return q
+
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
@@ -147,9 +162,17 @@ class DDIMSampler(object):
         if sc["sigma"] != 0.0 and noise is None:
             noise = noise_like(x.shape, x.device, repeat_noise)
         v = (sc["v_sqrt_a"], sc["v_sqrt_1ma"]) if getattr(self.model, "parameterization", "eps") == "v" else None
-        return ops.ddim_step(x.float().contiguous(), e_t, sc, noise=noise if sc["sigma"] != 0.0 else None,
-                             e_uncond=e_u, guidance=unconditional_guidance_scale, v_param=v,
-                             temperature=temperature)
+        x = x.float().contiguous()
+        noise = noise if sc["sigma"] != 0.0 else None
+        x_prev, pred_x0 = ops.ddim_step(x, e_t, sc, noise=noise, e_uncond=e_u, guidance=unconditional_guidance_scale,
+                                        v_param=v, temperature=temperature)
+        if not quantize_denoised:
+            return x_prev, pred_x0
+        # ddim.py:196-203: quantise pred_x0, then x_prev from the quantised value (same op order)
+        pred_x0, _ = self._quantizer().nearest(pred_x0)
+        ops.ddim_xprev(pred_x0, e_t, sc, x=x, noise=noise, e_uncond=e_u, guidance=unconditional_guidance_scale,
+                       v_param=v, x_prev=x_prev, temperature=temperature)
+        return x_prev, pred_x0
 
     # ------------------------------------------------------------------ img2img
     @torch.no_grad()
@@ -183,7 +206,7 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               use_original_steps=False):
+               use_original_steps=False, quantize_denoised=False):
         """Denoise from DDIM index ``t_start`` (``ddim.py:222-240``): timesteps[:t_start] walked in
         reverse, index = total_steps - i - 1, one fused HIP update per step."""
         if use_original_steps:
@@ -196,6 +219,7 @@ class DDIMSampler(object):
             index = total_steps - i - 1
             ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
             x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index, use_original_steps=use_original_steps,
+                                          quantize_denoised=quantize_denoised,
                                           unconditional_guidance_scale=unconditional_guidance_scale,
                                           unconditional_conditioning=unconditional_conditioning)
         return x_dec

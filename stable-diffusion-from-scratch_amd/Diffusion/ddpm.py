@@ -69,6 +69,19 @@ class DiffusionWrapper(nn.Module):
         raise NotImplementedError(f"sd_amd: conditioning_key={self.conditioning_key} is not on the txt2img path")
 
 
+def _is_vq(first_stage):
+    from ..vqvae.autoencoder import VQModelInterface
+    return isinstance(first_stage, VQModelInterface)
+
+
+def _first_stage_decode(first_stage, z, pre_scale, force_not_quantize=False):
+    """One first-stage decode of ``pre_scale * z``; a ``VQModelInterface`` quantises first unless
+    ``force_not_quantize`` (``Diffusion/ddpm.py:756-798``)."""
+    if _is_vq(first_stage):
+        return first_stage.decode(z, force_not_quantize=force_not_quantize, pre_scale=pre_scale)
+    return first_stage.decode(z, pre_scale=pre_scale)
+
+
 class LatentDiffusion(nn.Module):
     def __init__(self, first_stage_config, cond_stage_config=None, unet_config=None, num_timesteps_cond=None,
                  cond_stage_key="txt", cond_stage_trainable=False, concat_mode=True, cond_stage_forward=None,
@@ -150,8 +163,12 @@ class LatentDiffusion(nn.Module):
 
     @torch.no_grad()
     def encode_first_stage(self, x):
-        """``ldm/diffusion/ddpm.py:1237-1279`` (non-split branch): the first stage's posterior."""
-        return self.first_stage_model.encode(x)
+        """``ldm/diffusion/ddpm.py:1237-1279`` (non-split branch): the first stage's posterior; for a
+        ``VQModelInterface`` the pre-quantisation latent ``h`` of its ``(h, 0, info)`` tuple."""
+        enc = self.first_stage_model.encode(x)
+        if _is_vq(self.first_stage_model):
+            return enc[0]
+        return enc
 
     def get_first_stage_encoding(self, encoder_posterior, noise=None):
         """``ldm/diffusion/ddpm.py:795-806``: scale_factor * posterior sample (fused on the device)."""
@@ -165,11 +182,19 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False):
         """``ldm/diffusion/ddpm.py:1083-1156``: z / scale_factor → first-stage decode; with
-        ``split_input_params['patch_distributed_vq']`` the tiled (patch) decode."""
+        ``split_input_params['patch_distributed_vq']`` the tiled (patch) decode.  ``predict_cids``
+        (``:1086-1095``): z holds codebook indices, or 4-D per-class scores whose argmax over the
+        channels gives them; the codebook entries are decoded without quantising again."""
+        if predict_cids:
+            if z.dim() == 4:
+                z = torch.argmax(z.exp(), dim=1).long()
+            z = self.first_stage_model.quantize.get_codebook_entry(z, shape=None)
+            z = z.permute(0, 3, 1, 2).contiguous()
+        fnq = bool(predict_cids or force_not_quantize)
         sp = getattr(self, "split_input_params", None)
         if sp and sp.get("patch_distributed_vq"):
-            return self._decode_tiled(z, sp)
-        return self.first_stage_model.decode(z, pre_scale=1.0 / self.scale_factor)
+            return self._decode_tiled(z, sp, fnq)
+        return _first_stage_decode(self.first_stage_model, z, 1.0 / self.scale_factor, fnq)
 
     # ------------------------------------------------------------------ tiled decode (SURVEY §8(f) rank 4)
     @staticmethod
@@ -197,7 +222,7 @@ class LatentDiffusion(nn.Module):
             lw = np.clip(self.delta_border(Ly, Lx), lo, hi).astype(np.float32).reshape(-1)
         return pix, lw
 
-    def _decode_tiled(self, z, sp):
+    def _decode_tiled(self, z, sp, force_not_quantize=False):
         """Patch decode (``ldm/diffusion/ddpm.py:1097-1139`` + ``get_fold_unfold`` uf branch
         ``:894-960``): latent patches of ``ks`` every ``stride`` are decoded as one batch
         (chunks of ``sp.get('max_batch', 16)`` patches·images), weighted and overlap-added at
@@ -218,8 +243,8 @@ class LatentDiffusion(nn.Module):
         patches = ops.extract_patches(z.float(), ks[0], ks[1], stride[0], stride[1])   # [L, B, C, kh, kw]
         flat = patches.view(Ly * Lx * B, Cz, ks[0], ks[1])
         chunk = int(sp.get("max_batch", 16))
-        dec = [self.first_stage_model.decode(flat[i:i + chunk], pre_scale=1.0 / self.scale_factor)
-               for i in range(0, flat.shape[0], chunk)]
+        dec = [_first_stage_decode(self.first_stage_model, flat[i:i + chunk], 1.0 / self.scale_factor,
+                                   force_not_quantize) for i in range(0, flat.shape[0], chunk)]
         dec = torch.cat(dec, 0) if len(dec) > 1 else dec[0]
         dec = dec.view(Ly * Lx, B, dec.shape[1], dec.shape[2], dec.shape[3])
         return ops.fold_patches(dec, pix_w, l_w, h * uf, w * uf, stride[0] * uf, stride[1] * uf, Ly, Lx)

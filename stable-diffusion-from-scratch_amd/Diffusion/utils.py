@@ -12,7 +12,7 @@ import importlib
 
 _PKG = __name__.rsplit(".", 2)[0]      # "sd_amd"
 MIRRORED = ("openai_model", "Unet", "Encoder_Decoder", "VAE", "DDIM", "Diffusion", "DDPM", "clip_encoder",
-            "Distribution")
+            "Distribution", "vqvae")
 
 
 def get_obj_from_str(string, reload=False):

@@ -82,9 +82,10 @@ OUT_NHWC_F16, OUT_NCHW_F32, OUT_GEGLU_F16, OUT_ROWS_F32 = 0, 1, 2, 3
 ACT_NONE, ACT_QUICK_GELU = 0, 1
 
 EXPORTS = ["sdk_conv2d_plan", "sdk_conv2d", "sdk_group_norm_workspace", "sdk_group_norm_affine", "sdk_group_norm_apply", "sdk_group_norm_apply_padded", "sdk_group_norm_apply_ex", "sdk_group_norm", "sdk_group_norm_finalize", "sdk_layer_norm",
-           "sdk_attention", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
+           "sdk_attention", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
            "sdk_diag_gaussian_sample", "sdk_stochastic_encode", "sdk_token_embedding", "sdk_extract_patches",
-           "sdk_fold_patches", "sdk_upsample_bilinear2x", "sdk_upsample_nearest2x_padded", "sdk_gelu", "sdk_last_error", "sdk_version", "sdk_kernel_name",
+           "sdk_fold_patches", "sdk_vq_code_norms", "sdk_vq_nearest_splits", "sdk_vq_nearest", "sdk_vq_lookup", "sdk_vq_remap",
+           "sdk_upsample_bilinear2x", "sdk_upsample_nearest2x_padded", "sdk_gelu", "sdk_last_error", "sdk_version", "sdk_kernel_name",
            "sdk_probe_mfma_flops", "sdk_probe_mfma", "sdk_probe_copy", "sdk_probe_copy_ex"]
 
 _lib = None
@@ -130,6 +131,13 @@ def lib():
     L.sdk_token_linear.argtypes = [C.POINTER(TokenLinearArgs), vp]
     L.sdk_token_linear_ln.argtypes = [C.POINTER(TokenLinearArgs), vp, vp, f32, vp, i32, vp]
     L.sdk_ddim_step.argtypes = [C.POINTER(DdimArgs), vp]
+    L.sdk_ddim_xprev.argtypes = [C.POINTER(DdimArgs), vp]
+    L.sdk_vq_code_norms.argtypes = [vp, vp, i32, i32, vp]
+    L.sdk_vq_nearest_splits.argtypes = [i64, i32, i32]
+    L.sdk_vq_nearest_splits.restype = i32
+    L.sdk_vq_nearest.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, i32, vp]
+    L.sdk_vq_lookup.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp]
+    L.sdk_vq_remap.argtypes = [vp, vp, vp, vp, i64, i32, i32, i64, i32, vp]
     L.sdk_ddpm_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, vp]
     L.sdk_timestep_embedding.argtypes = [vp, vp, vp, i32, i32, vp]
     L.sdk_nchw_to_nhwc.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp]

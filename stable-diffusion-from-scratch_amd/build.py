@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsdk_amd.so")
-SOURCES = ["conv.hip", "norm.hip", "attention.hip", "sampler.hip", "xattn.hip", "ff.hip", "token.hip", "probe.hip"]
+SOURCES = ["conv.hip", "norm.hip", "attention.hip", "sampler.hip", "xattn.hip", "ff.hip", "token.hip", "vq.hip", "probe.hip"]
 # conv.hip is compiled once per part (its SDK_CONV_PART partition: host planner + small kernels, then the tile
 # kernel instantiations in four groups) so the objects build in parallel
 CONV_PARTS = 6
@@ -37,7 +37,7 @@ EXTRA = {"attention.hip": ["-mno-amdgpu-ieee", "-fno-honor-nans"]}
 # it is reported as a warning (it costs time: scratch round trips in the K loop)
 REMARK = "-Rpass-analysis=kernel-resource-usage"
 NO_SCRATCH = re.compile(r"token_linear320_kernel")
-WARN_SCRATCH = re.compile(r"conv_glds_kernel|conv_ph_kernel|ff_geglu_kernel|xattn_block_kernel|attn_fwd_kernel")
+WARN_SCRATCH = re.compile(r"conv_glds_kernel|conv_ph_kernel|ff_geglu_kernel|xattn_block_kernel|attn_fwd_kernel|vq_nearest_")
 _RES = re.compile(r"remark: (?:Function Name: (\S+)|\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+))")
 
 

@@ -69,6 +69,44 @@ __global__ void __launch_bounds__(256) ddim_step_kernel(sdk_ddim_args a) {
   }
 }
 
+// Second half of ddim_step_kernel for the quantize_denoised path (DDIM/ddim.py:196-203): pred_x0 is
+// an INPUT here (the caller quantised it in between); e is rebuilt from the same inputs by the same
+// operations, and x_prev by the same operations in the same order, so with the first call's own
+// pred_x0 the result equals that call's x_prev bit for bit.
+__global__ void __launch_bounds__(256) ddim_xprev_kernel(sdk_ddim_args a) {
+  const int64_t n4 = a.n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += stride) {
+    f4 e = reinterpret_cast<const f4*>(a.e)[i];
+    if (a.e_uncond) {
+      const f4 u = reinterpret_cast<const f4*>(a.e_uncond)[i];
+      f4 d;
+      for (int j = 0; j < 4; ++j) d[j] = e[j] - u[j];
+      for (int j = 0; j < 4; ++j) e[j] = u[j] + a.guidance * d[j];
+    }
+    if (a.v_param) {
+      const f4 x = reinterpret_cast<const f4*>(a.x)[i];
+      for (int j = 0; j < 4; ++j) {
+        const float t0 = a.v_sqrt_a * e[j];
+        const float t1 = a.v_sqrt_1ma * x[j];
+        e[j] = t0 + t1;
+      }
+    }
+    f4 nz = {0.f, 0.f, 0.f, 0.f};
+    if (a.noise) nz = reinterpret_cast<const f4*>(a.noise)[i];
+    const f4 p0 = reinterpret_cast<const f4*>(a.pred_x0)[i];
+    f4 xp;
+    for (int j = 0; j < 4; ++j) {
+      const float dir = a.dir_coef * e[j];
+      const float t3 = a.sqrt_a_prev * p0[j];
+      const float t4 = t3 + dir;
+      const float nn = (a.sigma * nz[j]) * a.temperature;
+      xp[j] = t4 + nn;
+    }
+    reinterpret_cast<f4*>(a.x_prev)[i] = xp;
+  }
+}
+
 __global__ void __launch_bounds__(256) ddpm_step_kernel(const float* x, const float* eps, const float* noise,
                                                         float* out, int64_t n, float inv_sqrt_alpha, float coef,
                                                         float sigma) {
@@ -326,6 +364,16 @@ extern "C" int sdk_ddim_step(const sdk_ddim_args* a, sdk_stream_t stream) {
   const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 2048);
   hipLaunchKernelGGL(ddim_step_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a);
   return check_launch("ddim_step");
+}
+
+extern "C" int sdk_ddim_xprev(const sdk_ddim_args* a, sdk_stream_t stream) {
+  if (!a || !a->e || !a->x_prev || !a->pred_x0 || (a->v_param && !a->x))
+    return fail(SDK_EINVAL, "ddim_xprev: null pointer");
+  if (a->n <= 0 || a->n % 4) return fail(SDK_EINVAL, "ddim_xprev: n must be a positive multiple of 4");
+  const int64_t n4 = a->n / 4;
+  const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 2048);
+  hipLaunchKernelGGL(ddim_xprev_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a);
+  return check_launch("ddim_xprev");
 }
 
 extern "C" int sdk_ddpm_step(const float* x, const float* eps, const float* noise, float* out, int64_t n,

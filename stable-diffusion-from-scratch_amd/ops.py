@@ -1132,6 +1132,135 @@ def ddim_step(x, e, sc: dict, noise=None, e_uncond=None, guidance=1.0, v_param=N
     return xp, p0
 
 
+def ddim_xprev(pred_x0, e, sc: dict, x=None, noise=None, e_uncond=None, guidance=1.0, v_param=None, x_prev=None,
+               temperature=1.0):
+    """Second half of ``ddim_step`` with ``pred_x0`` as an input (the quantize_denoised path quantises
+    it in between): x_prev = sqrt(a_prev)·pred_x0 + dir_coef·e + sigma·noise·temperature, the same
+    fp32 operations in the same order.  ``e`` / ``e_uncond`` / ``guidance`` / ``v_param`` are the
+    first call's; ``x`` is needed only with ``v_param``."""
+    _need_cuda(pred_x0, "ddim_xprev", torch.float32)
+    _need_cuda(e, "ddim_xprev", torch.float32)
+    if e.shape != pred_x0.shape:
+        raise ValueError(f"sd_amd.ddim_xprev: pred_x0 {tuple(pred_x0.shape)} vs e {tuple(e.shape)}")
+    pred_x0, e = pred_x0.contiguous(), e.contiguous()
+    a = DdimArgs()
+    xp = x_prev if x_prev is not None else torch.empty_like(pred_x0)
+    a.e, a.x_prev, a.pred_x0 = e.data_ptr(), xp.data_ptr(), pred_x0.data_ptr()
+    if e_uncond is not None:
+        e_uncond = e_uncond.contiguous()
+        a.e_uncond = e_uncond.data_ptr()
+    if noise is not None:
+        noise = noise.contiguous()
+        a.noise = noise.data_ptr()
+    a.n = pred_x0.numel()
+    a.dir_coef = float(sc["dir_coef"])
+    a.sqrt_a_prev = float(sc["sqrt_a_prev"])
+    a.sigma = float(sc["sigma"])
+    a.temperature = float(temperature)
+    a.guidance = float(guidance)
+    if v_param is not None:
+        if x is None:
+            raise ValueError("sd_amd.ddim_xprev: v_param needs x")
+        _need_cuda(x, "ddim_xprev", torch.float32)
+        x = x.contiguous()
+        a.x = x.data_ptr()
+        a.v_param = 1
+        a.v_sqrt_a, a.v_sqrt_1ma = float(v_param[0]), float(v_param[1])
+    check(lib().sdk_ddim_xprev(C.byref(a), _stream()), "ddim_xprev")
+    return xp
+
+
+# --------------------------------------------------------------------------- vector quantiser
+
+def _vq_codebook(codebook, what):
+    _need_cuda(codebook, what + " codebook", torch.float32)
+    if codebook.dim() != 2 or not codebook.is_contiguous():
+        raise ValueError(f"sd_amd.{what}: codebook must be a contiguous [n_e, e_dim] tensor")
+    return codebook.shape
+
+
+def vq_code_norms(codebook: torch.Tensor):
+    """‖e_j‖² per code, fp32 [n_e] — computed once per codebook and passed to ``vq_nearest``."""
+    N, D = _vq_codebook(codebook, "vq_code_norms")
+    norms = torch.empty(N, dtype=torch.float32, device=codebook.device)
+    check(lib().sdk_vq_code_norms(_ptr(codebook), _ptr(norms), N, D, _stream()), "vq_code_norms")
+    return norms
+
+
+def vq_nearest(z: torch.Tensor, codebook: torch.Tensor, norms: torch.Tensor = None, splits: int = 0):
+    """Nearest code per pixel of NCHW fp32 ``z`` [B, e_dim, H, W] → (z_q NCHW fp32, idx int64 [B·H·W]).
+    One fused search (no [M, n_e] distance matrix); lowest index wins ties; z_q = z + (e − z).
+    ``splits`` > 0 forces the number of codebook splits (tests), 0 lets the library choose."""
+    _need_cuda(z, "vq_nearest", torch.float32)
+    N, D = _vq_codebook(codebook, "vq_nearest")
+    if z.dim() != 4 or z.shape[1] != D:
+        raise ValueError(f"sd_amd.vq_nearest: z {tuple(z.shape)} does not match e_dim {D} (expected [B, {D}, H, W])")
+    if not 1 <= D <= 256:
+        raise ValueError(f"sd_amd.vq_nearest: e_dim {D} outside [1, 256]")
+    if z.numel() == 0:
+        raise ValueError("sd_amd.vq_nearest: empty input")
+    if norms is None:
+        norms = vq_code_norms(codebook)
+    _need_cuda(norms, "vq_nearest norms", torch.float32)
+    if norms.shape != (N,):
+        raise ValueError(f"sd_amd.vq_nearest: norms {tuple(norms.shape)} vs n_e {N}")
+    z = z.contiguous()
+    B, _, H, W = z.shape
+    M = B * H * W
+    zq = torch.empty_like(z)
+    idx = torch.empty(M, dtype=torch.int64, device=z.device)
+    keys = None
+    if splits > 1 or (splits <= 0 and lib().sdk_vq_nearest_splits(M, N, D) > 1):
+        keys = torch.empty(M, dtype=torch.int64, device=z.device)
+    check(lib().sdk_vq_nearest(_ptr(z), _ptr(codebook), _ptr(norms.contiguous()), _ptr(idx), _ptr(zq), B, D, H * W, N,
+                               _ptr(keys), M * 8 if keys is not None else 0, int(splits), _stream()), "vq_nearest")
+    return zq, idx
+
+
+def vq_lookup(idx: torch.Tensor, codebook: torch.Tensor, nchw_shape=None):
+    """codebook[idx]: int64 indices (any shape, M entries) → fp32 [M, e_dim], or NCHW
+    [B, e_dim, H, W] when ``nchw_shape`` = (B, H, W) is given.  Indices must already be inside
+    [0, n_e) (``VectorQuantize2.get_codebook_entry`` checks them on the host)."""
+    _need_cuda(idx, "vq_lookup", torch.int64)
+    N, D = _vq_codebook(codebook, "vq_lookup")
+    idx = idx.contiguous().view(-1)
+    M = idx.numel()
+    if M == 0:
+        raise ValueError("sd_amd.vq_lookup: no indices")
+    if nchw_shape is not None:
+        B, H, W = (int(v) for v in nchw_shape)
+        if B * H * W != M:
+            raise ValueError(f"sd_amd.vq_lookup: {M} indices do not fill {(B, H, W)}")
+        out = torch.empty(B, D, H, W, dtype=torch.float32, device=idx.device)
+        hw, nchw = H * W, 1
+    else:
+        out = torch.empty(M, D, dtype=torch.float32, device=idx.device)
+        hw, nchw = 1, 0
+    check(lib().sdk_vq_lookup(_ptr(idx), _ptr(codebook), _ptr(out), M, N, D, hw, nchw, _stream()), "vq_lookup")
+    return out
+
+
+def vq_remap(inds: torch.Tensor, used: torch.Tensor, *, to_used: bool, unknown: int = 0, random=None,
+             extra: bool = False):
+    """Index remap on the device.  ``to_used=True``: position of the first match in ``used`` else
+    ``random[i]`` (a pre-drawn int64 tensor) or ``unknown``; ``to_used=False`` (unmap_to_all):
+    ``used[inds]``, with ``extra`` an index ≥ len(used) becomes 0 first.  Shape is kept."""
+    _need_cuda(inds, "vq_remap", torch.int64)
+    _need_cuda(used, "vq_remap used", torch.int64)
+    if inds.numel() == 0 or used.dim() != 1 or used.numel() == 0:
+        raise ValueError("sd_amd.vq_remap: empty indices or used table")
+    src = inds.contiguous()
+    if random is not None:
+        _need_cuda(random, "vq_remap random", torch.int64)
+        if random.numel() != src.numel():
+            raise ValueError("sd_amd.vq_remap: random must have one entry per index")
+        random = random.contiguous()
+    out = torch.empty_like(src)
+    check(lib().sdk_vq_remap(_ptr(src), _ptr(used.contiguous()), _ptr(random), _ptr(out), src.numel(), used.numel(),
+                             0 if to_used else 1, int(unknown), 1 if extra else 0, _stream()), "vq_remap")
+    return out
+
+
 def diag_gaussian_sample(moments: torch.Tensor, noise=None, scale: float = 1.0, out=None):
     """moments NCHW fp32 [B, 2C, H, W] -> scale * (mean + std * noise) (or scale * mean) [B, C, H, W]."""
     _need_cuda(moments, "diag_gaussian_sample", torch.float32)
