@@ -360,6 +360,58 @@ int sdk_ddim_step(const sdk_ddim_args* a, sdk_stream_t stream);
  * the same order as sdk_ddim_step: fed that call's pred_x0 it reproduces its x_prev bit for bit. */
 int sdk_ddim_xprev(const sdk_ddim_args* a, sdk_stream_t stream);
 
+/* ---------------------------------------------------------------- ancestral sampler (LatentDiffusion.p_sample)
+ * Fused posterior step (ldm/diffusion/ddpm.py:1528-1636), fp32, every product and sum rounded on its own:
+ *   1. x_recon = c_recip*x - c_recipm1*model_out   (eps)   |   x_recon = model_out   (x0_param)
+ *   2. clip: x_recon = clamp(x_recon, -1, 1)
+ *   3. mean = coef1*x_recon + coef2*x
+ *   4. x_prev = mean + ((nonzero*sigma) * (noise*temperature))
+ * The scalars are the fp32 schedule entries at one timestep t (sqrt_recip_alphas_cumprod,
+ * sqrt_recipm1_alphas_cumprod, posterior_mean_coef1 / 2, sigma = exp(0.5*posterior_log_variance_clipped)
+ * evaluated by the caller on the host and correctly rounded to fp32, nonzero = t != 0); a batch with
+ * several t is one call per run of equal t.  stage 0: steps 1-4 (x_recon written when non-NULL).  stage 1: steps 1-2 only, x_recon is
+ * the output.  stage 2: steps 3-4 with x_recon_in as INPUT (quantize_denoised quantises it in between;
+ * no clamp is applied again) -- fed stage 1's x_recon it reproduces stage 0's x_prev bit for bit.
+ * noise may be NULL where nonzero == 0.  Any n >= 1; 16-byte accesses when every pointer is 16-byte
+ * aligned, scalar otherwise and for the tail.  x_prev may alias x; x_recon may alias model_out. */
+typedef struct {
+  const float* x; const float* model_out; const float* noise; const float* x_recon_in;
+  float* x_prev; float* x_recon;
+  int64_t n;
+  int32_t stage, x0_param, clip;
+  float c_recip, c_recipm1, coef1, coef2, sigma, nonzero, temperature;
+} sdk_posterior_args;
+
+int sdk_posterior_step(const sdk_posterior_args* a, sdk_stream_t stream);
+
+/* Known-region blend of p_sample_loop (ldm/diffusion/ddpm.py:1783-1784) at one timestep:
+ * out = (sqrt_acp*x0 + sqrt_1m_acp*noise)*mask + (1 - mask)*img, op by op in that order.  x0, noise, img,
+ * out: n = batch*per_sample fp32, per_sample = channels*hw.  The mask is read by index, never expanded:
+ * mask_mode 0 [batch][1][hw], 1 [1][1][hw], 2 [batch][channels][hw].  out may alias img. */
+typedef struct {
+  const float* x0; const float* noise; const float* mask; const float* img;
+  float* out;
+  int64_t n, per_sample;
+  int32_t hw, mask_mode;
+  float sqrt_acp, sqrt_1m_acp;
+} sdk_masked_q_args;
+
+int sdk_masked_q_sample(const sdk_masked_q_args* a, sdk_stream_t stream);
+
+/* sdk_nchw_to_nhwc (scale 1) of torch.cat(src, 1) without the concatenated fp32 tensor
+ * (DiffusionWrapper.forward 'concat' / 'hybrid', Diffusion/ddpm.py:51-63): nsrc (1..4) NCHW fp32 sources
+ * [batch][channels[i]][hw] -> y NHWC fp16 [batch][hw][c_pad]; source i lands at channel offset
+ * sum(channels[<i]), channels from the sum up to c_pad are zero. */
+typedef struct {
+  const float* src[4];
+  int32_t channels[4];
+  int32_t nsrc;
+  void* y;
+  int32_t batch, hw, c_pad;
+} sdk_concat_args;
+
+int sdk_concat_nchw_to_nhwc(const sdk_concat_args* a, sdk_stream_t stream);
+
 /* ---------------------------------------------------------------- vector quantiser (vqvae/quantize.py)
  * norms[j] = |codebook[j]|^2 (fp32 fma chain), computed once per codebook [n][d]. */
 int sdk_vq_code_norms(const float* codebook, float* norms, int32_t n, int32_t d, sdk_stream_t stream);

@@ -9,8 +9,9 @@ would hold (``ddim.py:189-192``), derived with torch's CPU fp32 ops.
 
 ``quantize_x0`` / ``quantize_denoised`` (``ddim.py:196-197``) run step → fused nearest-code search
 on ``pred_x0`` (``first_stage_model.quantize``) → ``sdk_ddim_xprev`` with the quantised value; ``decode``
-takes the flag as well (extension).  Masking, ``score_corrector``, ``noise_dropout`` and original-steps
-stay NotImplementedError.
+takes the flag as well (extension).  Masking, ``score_corrector``, ``noise_dropout``, original-steps and
+``parameterization == "x0"`` stay NotImplementedError (``LatentDiffusion.p_sample_loop`` takes x0 models and
+masks).  Dict conditionings with list values (``{"c_concat": [c]}``) are accepted.
 
 Extensions (documented, not in the reference): ``parameterization == "v"``
 on the model and an optional ``noise_fn(i, shape)`` hook
@@ -69,8 +70,10 @@ class DDIMSampler(object):
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, noise_fn=None, **kwargs):
         if conditioning is not None:
-            cbs = conditioning[list(conditioning.keys())[0]].shape[0] if isinstance(conditioning, dict) \
-                else conditioning.shape[0]
+            ctmp = conditioning[list(conditioning.keys())[0]] if isinstance(conditioning, dict) else conditioning
+            while isinstance(ctmp, list):          # {'c_concat': [c]}: the reference's .shape on the list fails
+                ctmp = ctmp[0]
+            cbs = ctmp.shape[0]
             if cbs != batch_size:
                 print(f"Warning: Got {cbs} conditionings but batch-size is {batch_size}")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
@@ -145,6 +148,9 @@ class DDIMSampler(object):
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, noise=None):
+        if getattr(self.model, "parameterization", "eps") == "x0":
+            raise NotImplementedError("sd_amd: x0-parameterised DDIM is not implemented (the ancestral sampler, "
+                                      "LatentDiffusion.p_sample_loop, takes x0 models)")
         b = x.shape[0]
         sc = self.step_scalars(index)
         e_u = None

@@ -1,6 +1,6 @@
 """Host-side schedule bookkeeping — mirror of ``DDIM/diffusion_modules.py`` (≡
 ``ldm/modules/diffusionmodules/util.py``) and ``DDPM.register_schedule``
-(``Diffusion/ddpm.py:195-253``).
+(``Diffusion/ddpm.py:195-253``, all twelve buffers: the q(x_t | x_0) ones and the posterior ones).
 
 These are one-time host constants (the reference computes them on the host
 too).  They are evaluated with the same torch/numpy dtype chain as the reference
@@ -38,17 +38,28 @@ def _beta_schedule(schedule, n_timestep, linear_start, linear_end, cosine_s):
 
 
 def register_schedule(timesteps=1000, linear_start=1e-4, linear_end=2e-2, beta_schedule="linear",
-                      given_betas=None, cosine_s=8e-3):
-    """fp32 buffers of ``DDPM.register_schedule`` (fp64 math)."""
+                      given_betas=None, cosine_s=8e-3, v_posterior=0.):
+    """fp32 buffers of ``DDPM.register_schedule`` (fp64 math, ``Diffusion/ddpm.py:215-253`` expression by
+    expression); ``v_posterior`` is the reference's ``self.v_posterior``."""
     betas = np.asarray(given_betas, dtype=np.float64) if given_betas is not None else \
         make_beta_schedule(beta_schedule, timesteps, linear_start, linear_end, cosine_s)
-    alphas_cumprod = np.cumprod(1.0 - betas, axis=0)
+    alphas = 1. - betas
+    alphas_cumprod = np.cumprod(alphas, axis=0)
     alphas_cumprod_prev = np.append(1.0, alphas_cumprod[:-1])
+    posterior_variance = (1 - v_posterior) * betas * (1. - alphas_cumprod_prev) / (
+        1. - alphas_cumprod) + v_posterior * betas
     # host constants: always CPU tensors, also when a model is built under torch.device("meta")
     f = lambda a: torch.tensor(a, dtype=torch.float32, device="cpu")
     return {"betas": f(betas), "alphas_cumprod": f(alphas_cumprod), "alphas_cumprod_prev": f(alphas_cumprod_prev),
             "sqrt_alphas_cumprod": f(np.sqrt(alphas_cumprod)),
             "sqrt_one_minus_alphas_cumprod": f(np.sqrt(1.0 - alphas_cumprod)),
+            "log_one_minus_alphas_cumprod": f(np.log(1. - alphas_cumprod)),
+            "sqrt_recip_alphas_cumprod": f(np.sqrt(1. / alphas_cumprod)),
+            "sqrt_recipm1_alphas_cumprod": f(np.sqrt(1. / alphas_cumprod - 1)),
+            "posterior_variance": f(posterior_variance),
+            "posterior_log_variance_clipped": f(np.log(np.maximum(posterior_variance, 1e-20))),
+            "posterior_mean_coef1": f(betas * np.sqrt(alphas_cumprod_prev) / (1. - alphas_cumprod)),
+            "posterior_mean_coef2": f((1. - alphas_cumprod_prev) * np.sqrt(alphas) / (1. - alphas_cumprod)),
             "num_timesteps": int(betas.shape[0])}
 
 

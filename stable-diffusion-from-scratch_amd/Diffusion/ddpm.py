@@ -2,7 +2,10 @@
 
 Kept: ``register_schedule`` buffers (``ddpm.py:195-253``), ``apply_model``
 conditioning wrapping (``ddpm.py:1139-1147,1269-1272`` → ``{'c_crossattn': [c]}``),
-``DiffusionWrapper.forward`` dispatch (``ddpm.py:46-73``), ``decode_first_stage``
+``DiffusionWrapper.forward`` dispatch (``ddpm.py:46-73``: None, 'crossattn', 'concat' and 'hybrid' — the
+channel concat is folded into the UNet's input pack; 'adm' raises, the UNet has no class head),
+LatentDiffusion's ancestral sampler (``ldm/diffusion/ddpm.py:1528-1811``: ``q_sample`` …
+``p_sample_loop`` / ``sample`` with ``clip_denoised``, ``quantize_denoised``, ``mask`` / ``x0``), ``decode_first_stage``
 with the CompVis scaling ``z / scale_factor`` (``ldm/diffusion/ddpm.py:1095``;
 ``Diffusion/ddpm.py:728`` drops z — SURVEY Q8), ``parameterization``.
 ``cond_stage_config`` is instantiated as the reference does (``ddpm.py:568-587``:
@@ -12,9 +15,13 @@ with the CompVis scaling ``z / scale_factor`` (``ldm/diffusion/ddpm.py:1095``;
 ``use_graphs(True)`` makes ``DiffusionWrapper.forward`` replay one HIP graph per UNet call
 (``graphs.GraphedUNet``) — same chain apply_model → DiffusionWrapper.forward → UNetModel,
 one hipGraphLaunch per step instead of ~600 kernel launches.
+Refused (NotImplementedError): ``score_corrector``, ``noise_dropout``, ``return_codebook_ids``,
+``shorten_cond_schedule``, ``progressive_denoising``.
 Out of scope (training / Lightning): losses, EMA, optimisers, data, logging.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
@@ -54,11 +61,12 @@ class DiffusionWrapper(nn.Module):
                 raise ValueError("sd_amd: timesteps must be integral")
         return t.to(device=device, dtype=torch.long)
 
-    def _unet(self, x, t, context=None):
+    def _unet(self, x, t, context=None, concat=None):
         t = self._int_timesteps(t, x.device)
+        kw = {"concat": list(concat)} if concat else {}
         if self._graphs_on:
-            return self._graphed(x, t.reshape(-1).expand(x.shape[0]), context)
-        return self.diffusion_model(x, t, context=context)
+            return self._graphed(x, t.reshape(-1).expand(x.shape[0]), context, **kw)
+        return self.diffusion_model(x, t, context=context, **kw)
 
     def forward(self, x, t, c_concat: list = None, c_crossattn: list = None):
         if self.conditioning_key is None:
@@ -66,7 +74,18 @@ class DiffusionWrapper(nn.Module):
         if self.conditioning_key == "crossattn":
             cc = c_crossattn[0] if len(c_crossattn) == 1 else torch.cat(c_crossattn, 1)
             return self._unet(x, t, context=cc)
-        raise NotImplementedError(f"sd_amd: conditioning_key={self.conditioning_key} is not on the txt2img path")
+        if self.conditioning_key in ("concat", "hybrid"):
+            # Diffusion/ddpm.py:51-63: torch.cat([x] + c_concat, 1) — done inside the UNet's input pack
+            if not c_concat:
+                raise ValueError(f"sd_amd: conditioning_key={self.conditioning_key} needs c_concat")
+            cc = None
+            if self.conditioning_key == "hybrid":
+                if not c_crossattn:
+                    raise ValueError("sd_amd: conditioning_key=hybrid needs c_crossattn")
+                cc = c_crossattn[0] if len(c_crossattn) == 1 else torch.cat(c_crossattn, 1)
+            return self._unet(x, t, context=cc, concat=c_concat)
+        raise NotImplementedError(f"sd_amd: conditioning_key={self.conditioning_key} needs a class-conditional "
+                                  "UNet (no class head in this UNetModel)")
 
 
 def _is_vq(first_stage):
@@ -88,12 +107,15 @@ class LatentDiffusion(nn.Module):
                  conditioning_key=None, scale_factor=1.0, scale_by_std=False, timesteps=1000,
                  beta_schedule="linear", linear_start=1e-4, linear_end=2e-2, cosine_s=8e-3, given_betas=None,
                  parameterization="eps", image_size=256, channels=3, first_stage_key="image", log_every_t=100,
-                 **ignored):
+                 clip_denoised=True, v_posterior=0., **ignored):
         super().__init__()
         assert parameterization in ["eps", "x0", "v"], "eps / x0 (reference) or v (extension, SURVEY Q9)"
-        if parameterization == "x0":
-            raise NotImplementedError("sd_amd: x0-parameterised DDIM is not on the txt2img path")
+        # x0 runs through the ancestral sampler (p_sample_loop); DDIMSampler.p_sample_ddim refuses it
         self.parameterization = parameterization
+        self.clip_denoised = clip_denoised
+        self.v_posterior = v_posterior
+        self.num_timesteps_cond = 1 if num_timesteps_cond is None else num_timesteps_cond
+        self.shorten_cond_schedule = self.num_timesteps_cond > 1
         if conditioning_key is None:
             conditioning_key = "concat" if concat_mode else "crossattn"
         if cond_stage_config == "__is_unconditional__":
@@ -109,10 +131,20 @@ class LatentDiffusion(nn.Module):
         self.image_size = image_size
         self.channels = channels
         self.log_every_t = log_every_t
-        sch = register_schedule(timesteps, linear_start, linear_end, beta_schedule, given_betas, cosine_s)
+        self.register_schedule(given_betas=given_betas, beta_schedule=beta_schedule, timesteps=timesteps,
+                               linear_start=linear_start, linear_end=linear_end, cosine_s=cosine_s)
+
+    def register_schedule(self, given_betas=None, beta_schedule="linear", timesteps=1000, linear_start=1e-4,
+                          linear_end=2e-2, cosine_s=8e-3):
+        """``DDPM.register_schedule`` (``Diffusion/ddpm.py:195-253``): the twelve fp32 buffers, with
+        ``self.v_posterior`` in the posterior variance (the training-only ``lvlb_weights`` is left out)."""
+        sch = register_schedule(timesteps, linear_start, linear_end, beta_schedule, given_betas, cosine_s,
+                                v_posterior=getattr(self, "v_posterior", 0.))
         self.num_timesteps = sch.pop("num_timesteps")
+        self.linear_start, self.linear_end = linear_start, linear_end
         for k, v in sch.items():
             self.register_buffer(k, v)
+        self._post_cache = None
 
     @property
     def device(self):
@@ -160,6 +192,234 @@ class LatentDiffusion(nn.Module):
         if self.model.conditioning_key is None:
             return self.model(x_noisy, t)
         return self.model(x_noisy, t, **cond)
+
+    # ------------------------------------------------------------------ ancestral sampler
+    # LatentDiffusion's own sampler (``ldm/diffusion/ddpm.py:1528-1811``; the reference's
+    # ``sample_log(ddim=False)`` path) on three fused HIP kernels: ``sdk_posterior_step`` (predict x0 →
+    # clamp → posterior mean → + σ·noise, one launch; two with the nearest-code search of
+    # ``quantize_denoised`` in between), ``sdk_masked_q_sample`` (known-region blend) and
+    # ``sdk_stochastic_encode`` (q_sample).  fp32, no contraction: bit-identical to the reference's
+    # expressions on the same inputs.  Reference quirks resolved as CompVis does:
+    # q_sample draws Gaussian noise (ldm's copy draws ``rand_like``), ``p_sample(return_x0=True)`` ADDS
+    # the noise term (ldm ``:1633`` multiplies), ``posterior_variance`` is spelt correctly, nothing is
+    # forced onto ``cuda:0``.
+    def _host_tables(self):
+        """Host fp32 copies of the per-timestep scalars the kernels take, and
+        σ_t = exp(0.5·posterior_log_variance_clipped[t]), the reference's ``(0.5 * model_log_variance).exp()``,
+        as the correctly rounded fp32 value (libm's fp64 exp, rounded once).  torch's own CPU fp32 ``exp`` is
+        within 1 ulp of it but depends on the host (its AVX2 and AVX-512 paths differ in the last bit for
+        some entries), which would make a run irreproducible across machines; rebuilt when the buffers change."""
+        lv = self.posterior_log_variance_clipped
+        key = (lv.data_ptr(), lv._version, self.posterior_mean_coef1.data_ptr(), self.sqrt_alphas_cumprod.data_ptr())
+        ent = getattr(self, "_post_cache", None)
+        if ent is not None and ent[0] == key:
+            return ent[1]
+        host = lambda b: b.detach().to("cpu", torch.float32)      # noqa: E731
+        tab = {"c_recip": host(self.sqrt_recip_alphas_cumprod).numpy(),
+               "c_recipm1": host(self.sqrt_recipm1_alphas_cumprod).numpy(),
+               "coef1": host(self.posterior_mean_coef1).numpy(), "coef2": host(self.posterior_mean_coef2).numpy(),
+               "sigma": np.asarray([math.exp(0.5 * float(v)) for v in host(lv).tolist()], dtype=np.float32),
+               "sqrt_acp": host(self.sqrt_alphas_cumprod).numpy(),
+               "sqrt_1m_acp": host(self.sqrt_one_minus_alphas_cumprod).numpy()}
+        self._post_cache = (key, tab)
+        return tab
+
+    def _host_t(self, t, b):
+        """Timesteps as a list of ``b`` host ints, range-checked (a device ``t`` costs one sync; the
+        sampler loop passes host ints)."""
+        if torch.is_tensor(t):
+            t = t.reshape(-1).tolist()
+        elif not isinstance(t, (list, tuple)):
+            t = [t]
+        t = [int(v) for v in t]
+        if len(t) == 1:
+            t = t * b
+        if len(t) != b or not all(0 <= v < self.num_timesteps for v in t):
+            raise ValueError(f"sd_amd: timesteps {t} for a batch of {b} and {self.num_timesteps} steps")
+        return t
+
+    @staticmethod
+    def _f32(x):
+        return x.float().contiguous()
+
+    def _bcast(self, buf, t, x):
+        tt = torch.as_tensor(t, device=buf.device, dtype=torch.long)
+        return buf[tt].reshape(len(t), *((1,) * (x.dim() - 1))).to(x.device)
+
+    @torch.no_grad()
+    def q_sample(self, x_start, t, noise=None):
+        """q(x_t | x_0) = sqrt_alphas_cumprod[t]·x_start + sqrt_one_minus_alphas_cumprod[t]·noise with
+        Gaussian noise (``Diffusion/ddpm.py:326-342``), per-sample ``t``."""
+        x_start = self._f32(x_start)
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        noise = noise.to(device=x_start.device, dtype=torch.float32).contiguous()
+        tab = self._host_tables()
+        out = torch.empty_like(x_start)
+        for b0, b1, ti in ops._t_runs(self._host_t(t, x_start.shape[0]), x_start.shape[0]):
+            ops.stochastic_encode(x_start[b0:b1], noise[b0:b1], float(tab["sqrt_acp"][ti]),
+                                  float(tab["sqrt_1m_acp"][ti]), out=out[b0:b1])
+        return out
+
+    @torch.no_grad()
+    def predict_start_from_noise(self, x_t, t, noise):
+        x_t = self._f32(x_t)
+        return ops.posterior_step(x_t, self._f32(noise), self._host_t(t, x_t.shape[0]), self._host_tables(),
+                                  stage=1)[1]
+
+    @torch.no_grad()
+    def q_posterior(self, x_start, x_t, t):
+        """(posterior mean, variance, clipped log-variance) of q(x_{t-1} | x_t, x_0); the last two are
+        the ``[b, 1, 1, 1]`` table entries as the reference's ``extract_into_tensor`` returns them."""
+        x_t = self._f32(x_t)
+        th = self._host_t(t, x_t.shape[0])
+        mean = self._posterior_mean(self._f32(x_start), x_t, th)
+        return mean, self._bcast(self.posterior_variance, th, x_t), \
+            self._bcast(self.posterior_log_variance_clipped, th, x_t)
+
+    def _posterior_mean(self, x_recon, x, th):
+        # stage 2 without noise: the noise term is (0·σ)·(0·T) = 0, x_prev = mean + 0
+        return ops.posterior_step(x, None, th, self._host_tables(), stage=2, x_recon_in=x_recon)[0]
+
+    def _refuse(self, return_codebook_ids=False, score_corrector=None, noise_dropout=0.):
+        if return_codebook_ids:
+            raise NotImplementedError("sd_amd: return_codebook_ids is not implemented (the reference dropped it)")
+        if score_corrector is not None:
+            raise NotImplementedError("sd_amd: score_corrector is not implemented by the ancestral sampler")
+        if noise_dropout > 0:
+            raise NotImplementedError("sd_amd: noise_dropout is not implemented by the ancestral sampler")
+
+    def _quantizer(self):
+        q = getattr(getattr(self, "first_stage_model", None), "quantize", None)
+        if q is None or not hasattr(q, "nearest"):
+            raise AttributeError("sd_amd.LatentDiffusion: quantize_denoised needs a VQ first stage "
+                                 "(first_stage_model.quantize); this model's first stage has no quantizer")
+        return q
+
+    def _x_recon(self, x, model_out, th, clip_denoised, quantize_denoised):
+        if self.parameterization not in ("eps", "x0"):
+            raise NotImplementedError(f"sd_amd: the ancestral sampler takes eps / x0 models, not "
+                                      f"'{self.parameterization}'")
+        x_recon = ops.posterior_step(x, model_out, th, self._host_tables(), stage=1, clip=clip_denoised,
+                                     x0_param=self.parameterization == "x0")[1]
+        if quantize_denoised:
+            x_recon, _ = self._quantizer().nearest(x_recon)
+        return x_recon
+
+    @torch.no_grad()
+    def p_mean_variance(self, x, c, t, clip_denoised: bool, return_codebook_ids=False, quantize_denoised=False,
+                        return_x0=False, score_corrector=None, corrector_kwargs=None):
+        self._refuse(return_codebook_ids, score_corrector)
+        x = self._f32(x)
+        th = self._host_t(t, x.shape[0])
+        model_out = self._f32(self.apply_model(x, t, c))
+        x_recon = self._x_recon(x, model_out, th, clip_denoised, quantize_denoised)
+        out = (self._posterior_mean(x_recon, x, th), self._bcast(self.posterior_variance, th, x),
+               self._bcast(self.posterior_log_variance_clipped, th, x))
+        return out + (x_recon,) if return_x0 else out
+
+    @torch.no_grad()
+    def p_sample(self, x, c, t, clip_denoised=False, repeat_noise=False, return_codebook_ids=False,
+                 quantize_denoised=False, return_x0=False, temperture=1., noise_dropout=0., score_corrector=None,
+                 corrector_kwargs=None, temperature=None, noise=None, t_host=None):
+        """One ancestral step x_t → x_{t-1}.  ``temperture`` is the reference's spelling; ``temperature``
+        (when given) overrides it.  Extensions: ``noise`` (recorded noise instead of a fresh draw) and
+        ``t_host`` (``t`` as host ints, saving the device read of ``t``)."""
+        self._refuse(return_codebook_ids, score_corrector, noise_dropout)
+        if self.parameterization not in ("eps", "x0"):
+            raise NotImplementedError(f"sd_amd: the ancestral sampler takes eps / x0 models, not "
+                                      f"'{self.parameterization}'")
+        temp = float(temperture if temperature is None else temperature)
+        x = self._f32(x)
+        th = self._host_t(t if t_host is None else t_host, x.shape[0])
+        model_out = self._f32(self.apply_model(x, t, c))
+        if noise is None:
+            from ..DDIM.diffusion_modules import noise_like
+            noise = noise_like(x.shape, x.device, repeat_noise)
+        noise = noise.to(device=x.device, dtype=torch.float32).contiguous()
+        tab = self._host_tables()
+        kw = dict(temperature=temp)
+        if not quantize_denoised:
+            x_prev, x0 = ops.posterior_step(x, model_out, th, tab, noise=noise, clip=clip_denoised,
+                                            x0_param=self.parameterization == "x0", want_x_recon=return_x0, **kw)
+        else:
+            x0 = self._x_recon(x, model_out, th, clip_denoised, True)
+            x_prev, _ = ops.posterior_step(x, None, th, tab, noise=noise, stage=2, x_recon_in=x0, **kw)
+        return (x_prev, x0) if return_x0 else x_prev
+
+    def progressive_denoising(self, *args, **kwargs):
+        raise NotImplementedError("sd_amd: progressive_denoising is not implemented (use p_sample_loop)")
+
+    @torch.no_grad()
+    def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None,
+                      timesteps=None, quantize_denoised=False, mask=None, x0=None, img_callback=None, start_T=None,
+                      log_every_t=None, temperature=1., noise_fn=None, q_noise_fn=None):
+        """``ldm/diffusion/ddpm.py:1745-1793``.  Extensions: ``temperature``, and the hooks
+        ``noise_fn(i, shape)`` / ``q_noise_fn(i, shape)`` that supply the step noise and the q_sample
+        noise of the mask blend at timestep ``i`` (reproducible runs, as DDIMSampler's ``noise_fn``)."""
+        if getattr(self, "shorten_cond_schedule", False):
+            raise NotImplementedError("sd_amd: shorten_cond_schedule (num_timesteps_cond > 1) is not implemented")
+        if not log_every_t:
+            log_every_t = self.log_every_t
+        device = self.betas.device
+        b = shape[0]
+        img = torch.randn(tuple(shape), device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
+        img = img.contiguous()
+        intermediates = [img]
+        if timesteps is None:
+            timesteps = self.num_timesteps
+        if start_T is not None:
+            timesteps = min(timesteps, start_T)
+        if mask is not None:
+            if x0 is None:
+                raise ValueError("sd_amd: mask needs x0 (the known region's latent)")
+            if x0.shape[2:] != mask.shape[2:]:
+                raise ValueError(f"sd_amd: mask {tuple(mask.shape)} and x0 {tuple(x0.shape)} differ in spatial size")
+            mask = mask.to(device=device, dtype=torch.float32)
+            x0 = x0.to(device=device, dtype=torch.float32)
+        if quantize_denoised:
+            self._quantizer()
+        tab = self._host_tables()
+        for i in reversed(range(0, timesteps)):
+            ts = torch.full((b,), i, device=device, dtype=torch.long)
+            img = self.p_sample(img, cond, ts, clip_denoised=self.clip_denoised, quantize_denoised=quantize_denoised,
+                                temperature=temperature, t_host=i,
+                                noise=noise_fn(i, img.shape) if noise_fn is not None else None)
+            if mask is not None:
+                qn = q_noise_fn(i, img.shape) if q_noise_fn is not None else torch.randn_like(x0)
+                img = ops.masked_q_sample(x0, qn.to(device=device, dtype=torch.float32), mask, img, i,
+                                          tab["sqrt_acp"], tab["sqrt_1m_acp"], out=img)
+            if i % log_every_t == 0 or i == timesteps - 1:
+                intermediates.append(img)
+            if callback:
+                callback(i)
+            if img_callback:
+                img_callback(img, i)
+        if return_intermediates:
+            return img, intermediates
+        return img
+
+    @torch.no_grad()
+    def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, verbose=True, timesteps=None,
+               quantize_denoised=False, mask=None, x0=None, shape=None, **kwargs):
+        """``ldm/diffusion/ddpm.py:1796-1811``; of ``kwargs`` the p_sample_loop extensions are passed on
+        (the reference drops them all)."""
+        if shape is None:
+            shape = (batch_size, self.channels, self.image_size, self.image_size)
+        if cond is not None:
+            if isinstance(cond, dict):
+                cond = {key: cond[key][:batch_size] if not isinstance(cond[key], list) else
+                        list(map(lambda x: x[:batch_size], cond[key])) for key in cond}
+            else:
+                cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+        if "temperture" in kwargs:
+            kwargs.setdefault("temperature", kwargs.pop("temperture"))
+        self._refuse(kwargs.pop("return_codebook_ids", False), kwargs.pop("score_corrector", None),
+                     kwargs.pop("noise_dropout", 0.))
+        extra = {k: kwargs[k] for k in ("temperature", "noise_fn", "q_noise_fn", "callback", "img_callback",
+                                        "start_T", "log_every_t") if k in kwargs}
+        return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose,
+                                  timesteps=timesteps, quantize_denoised=quantize_denoised, mask=mask, x0=x0, **extra)
 
     @torch.no_grad()
     def encode_first_stage(self, x):

@@ -78,11 +78,27 @@ class DdimArgs(C.Structure):
                 ("v_sqrt_1ma", f32)]
 
 
+class PosteriorArgs(C.Structure):
+    _fields_ = [("x", vp), ("model_out", vp), ("noise", vp), ("x_recon_in", vp), ("x_prev", vp), ("x_recon", vp),
+                ("n", i64), ("stage", i32), ("x0_param", i32), ("clip", i32), ("c_recip", f32), ("c_recipm1", f32),
+                ("coef1", f32), ("coef2", f32), ("sigma", f32), ("nonzero", f32), ("temperature", f32)]
+
+
+class MaskedQArgs(C.Structure):
+    _fields_ = [("x0", vp), ("noise", vp), ("mask", vp), ("img", vp), ("out", vp), ("n", i64), ("per_sample", i64),
+                ("hw", i32), ("mask_mode", i32), ("sqrt_acp", f32), ("sqrt_1m_acp", f32)]
+
+
+class ConcatArgs(C.Structure):
+    _fields_ = [("src", vp * 4), ("channels", i32 * 4), ("nsrc", i32), ("y", vp), ("batch", i32), ("hw", i32),
+                ("c_pad", i32)]
+
+
 OUT_NHWC_F16, OUT_NCHW_F32, OUT_GEGLU_F16, OUT_ROWS_F32 = 0, 1, 2, 3
 ACT_NONE, ACT_QUICK_GELU = 0, 1
 
 EXPORTS = ["sdk_conv2d_plan", "sdk_conv2d", "sdk_group_norm_workspace", "sdk_group_norm_affine", "sdk_group_norm_apply", "sdk_group_norm_apply_padded", "sdk_group_norm_apply_ex", "sdk_group_norm", "sdk_group_norm_finalize", "sdk_layer_norm",
-           "sdk_attention", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
+           "sdk_attention", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_posterior_step", "sdk_masked_q_sample", "sdk_concat_nchw_to_nhwc", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
            "sdk_diag_gaussian_sample", "sdk_stochastic_encode", "sdk_token_embedding", "sdk_extract_patches",
            "sdk_fold_patches", "sdk_vq_code_norms", "sdk_vq_nearest_splits", "sdk_vq_nearest", "sdk_vq_lookup", "sdk_vq_remap",
            "sdk_upsample_bilinear2x", "sdk_upsample_nearest2x_padded", "sdk_gelu", "sdk_last_error", "sdk_version", "sdk_kernel_name",
@@ -132,6 +148,9 @@ def lib():
     L.sdk_token_linear_ln.argtypes = [C.POINTER(TokenLinearArgs), vp, vp, f32, vp, i32, vp]
     L.sdk_ddim_step.argtypes = [C.POINTER(DdimArgs), vp]
     L.sdk_ddim_xprev.argtypes = [C.POINTER(DdimArgs), vp]
+    L.sdk_posterior_step.argtypes = [C.POINTER(PosteriorArgs), vp]
+    L.sdk_masked_q_sample.argtypes = [C.POINTER(MaskedQArgs), vp]
+    L.sdk_concat_nchw_to_nhwc.argtypes = [C.POINTER(ConcatArgs), vp]
     L.sdk_vq_code_norms.argtypes = [vp, vp, i32, i32, vp]
     L.sdk_vq_nearest_splits.argtypes = [i64, i32, i32]
     L.sdk_vq_nearest_splits.restype = i32

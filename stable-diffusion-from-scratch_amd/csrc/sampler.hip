@@ -119,6 +119,122 @@ __global__ void __launch_bounds__(256) ddpm_step_kernel(const float* x, const fl
   }
 }
 
+// ---- ancestral (posterior) sampler, LatentDiffusion.p_sample (ldm/diffusion/ddpm.py:1528-1636).
+// One element of the update; every product and sum is rounded on its own (contraction is off), in the
+// order torch evaluates predict_start_from_noise -> clamp_ -> q_posterior -> mean + mask*std*(noise*T).
+// `xr` carries x_recon: computed here for stage 0 / 1, the caller's (quantised) value for stage 2.
+__device__ __forceinline__ float posterior_recon(const sdk_posterior_args& a, float x, float m) {
+  float xr = m;
+  if (!a.x0_param) {
+    const float t0 = a.c_recip * x;
+    const float t1 = a.c_recipm1 * m;
+    xr = t0 - t1;
+  }
+  if (a.clip) xr = fminf(fmaxf(xr, -1.f), 1.f);
+  return xr;
+}
+
+__device__ __forceinline__ float posterior_xprev(const sdk_posterior_args& a, float x, float xr, float nz) {
+  const float t2 = a.coef1 * xr;
+  const float t3 = a.coef2 * x;
+  const float mean = t2 + t3;
+  const float s = a.nonzero * a.sigma;
+  const float nt = nz * a.temperature;
+  const float sn = s * nt;
+  return mean + sn;
+}
+
+// n4 16-byte groups (0 when a pointer is not 16-byte aligned), then the scalar tail [4 n4, n)
+__global__ void __launch_bounds__(256) posterior_step_kernel(sdk_posterior_args a, int64_t n4) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const bool need_m = a.stage != 2, need_x = a.stage != 1 || !a.x0_param;
+  for (int64_t i = tid; i < n4; i += stride) {
+    f4 x = {0.f, 0.f, 0.f, 0.f}, m = x, nz = x, xr, xp;
+    if (need_x) x = reinterpret_cast<const f4*>(a.x)[i];
+    if (need_m) m = reinterpret_cast<const f4*>(a.model_out)[i];
+    if (a.stage == 2) xr = reinterpret_cast<const f4*>(a.x_recon_in)[i];
+    else
+      for (int j = 0; j < 4; ++j) xr[j] = posterior_recon(a, x[j], m[j]);
+    if (a.x_recon) reinterpret_cast<f4*>(a.x_recon)[i] = xr;
+    if (a.stage == 1) continue;
+    if (a.noise) nz = reinterpret_cast<const f4*>(a.noise)[i];
+    for (int j = 0; j < 4; ++j) xp[j] = posterior_xprev(a, x[j], xr[j], nz[j]);
+    reinterpret_cast<f4*>(a.x_prev)[i] = xp;
+  }
+  for (int64_t i = 4 * n4 + tid; i < a.n; i += stride) {
+    const float x = need_x ? a.x[i] : 0.f;
+    const float xr = a.stage == 2 ? a.x_recon_in[i] : posterior_recon(a, x, need_m ? a.model_out[i] : 0.f);
+    if (a.x_recon) a.x_recon[i] = xr;
+    if (a.stage == 1) continue;
+    a.x_prev[i] = posterior_xprev(a, x, xr, a.noise ? a.noise[i] : 0.f);
+  }
+}
+
+// img = (sa x0 + s1m noise) mask + (1 - mask) img  (ldm/diffusion/ddpm.py:1783-1784), the mask read by
+// index: mask_mode 0 [B,1,H,W], 1 [1,1,H,W], 2 [B,C,H,W]
+__device__ __forceinline__ float masked_q_elem(const sdk_masked_q_args& a, int64_t i, float x0, float nz, float im) {
+  int64_t mi = i;
+  if (a.mask_mode == 0) mi = (i / a.per_sample) * a.hw + i % a.hw;
+  else if (a.mask_mode == 1) mi = i % a.hw;
+  const float mk = a.mask[mi];
+  const float t0 = a.sqrt_acp * x0;
+  const float t1 = a.sqrt_1m_acp * nz;
+  const float q = t0 + t1;
+  const float t2 = q * mk;
+  const float om = 1.f - mk;
+  const float t3 = om * im;
+  return t2 + t3;
+}
+
+__global__ void __launch_bounds__(256) masked_q_sample_kernel(sdk_masked_q_args a, int64_t n4) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  for (int64_t i = tid; i < n4; i += stride) {
+    const f4 x0 = reinterpret_cast<const f4*>(a.x0)[i];
+    const f4 nz = reinterpret_cast<const f4*>(a.noise)[i];
+    const f4 im = reinterpret_cast<const f4*>(a.img)[i];
+    f4 o;
+    for (int j = 0; j < 4; ++j) o[j] = masked_q_elem(a, 4 * i + j, x0[j], nz[j], im[j]);
+    reinterpret_cast<f4*>(a.out)[i] = o;
+  }
+  for (int64_t i = 4 * n4 + tid; i < a.n; i += stride) a.out[i] = masked_q_elem(a, i, a.x0[i], a.noise[i], a.img[i]);
+}
+
+// channel c of the concat of the sources at (b, pix); zero from the channel sum up to c_pad
+__device__ __forceinline__ float concat_fetch(const sdk_concat_args& a, int64_t b, int64_t pix, int c) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {   // constant trip count: src[] / channels[] stay in scalar registers
+    if (s >= a.nsrc) break;
+    if (c < a.channels[s]) return a.src[s][(b * a.channels[s] + c) * a.hw + pix];
+    c -= a.channels[s];
+  }
+  return 0.f;
+}
+
+// items [0, nvec): one 8-channel group of one pixel, a 16-byte store (consecutive lanes take consecutive
+// pixels, so the NCHW reads coalesce); items [nvec, nvec + nscal): one channel past the last full group
+__global__ void __launch_bounds__(256) concat_nchw_to_nhwc_kernel(sdk_concat_args a, int ngrp, int64_t nvec,
+                                                                  int64_t nscal) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t bhw = (int64_t)a.batch * a.hw;
+  half_t* y = reinterpret_cast<half_t*>(a.y);
+  for (int64_t e = tid; e < nvec; e += stride) {
+    const int g = (int)(e / bhw);
+    const int64_t r = e - g * bhw, b = r / a.hw, pix = r - b * a.hw;
+    h8 o;
+    for (int j = 0; j < 8; ++j) o[j] = (half_t)concat_fetch(a, b, pix, 8 * g + j);
+    *reinterpret_cast<h8*>(y + r * a.c_pad + 8 * g) = o;
+  }
+  const int c0 = 8 * ngrp;
+  for (int64_t e = tid; e < nscal; e += stride) {
+    const int c = c0 + (int)(e / bhw);
+    const int64_t r = e % bhw, b = r / a.hw, pix = r - b * a.hw;
+    y[r * a.c_pad + c] = (half_t)concat_fetch(a, b, pix, c);
+  }
+}
+
 __global__ void temb_kernel(const int64_t* t, const float* freqs, half_t* out, int batch, int dim) {
   const int half = dim / 2;
   const int b = blockIdx.x;
@@ -400,6 +516,56 @@ extern "C" int sdk_nchw_to_nhwc(const float* x, void* y, int32_t batch, int32_t 
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((hw + 63) / 64, batch), dim3(256), 0, (hipStream_t)stream, x,
                      (half_t*)y, channels, hw, c_pad, scale);
   return check_launch("nchw_to_nhwc");
+}
+
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+extern "C" int sdk_posterior_step(const sdk_posterior_args* a, sdk_stream_t stream) {
+  if (!a || a->n <= 0 || a->stage < 0 || a->stage > 2) return fail(SDK_EINVAL, "posterior_step: bad n / stage");
+  const bool need_m = a->stage != 2, need_x = a->stage != 1 || !a->x0_param;
+  if ((need_x && !a->x) || (need_m && !a->model_out) || (a->stage == 2 && !a->x_recon_in) ||
+      (a->stage != 1 && !a->x_prev) || (a->stage == 1 && !a->x_recon))
+    return fail(SDK_EINVAL, "posterior_step: null pointer");
+  if (a->stage != 1 && !a->noise && a->nonzero != 0.f)
+    return fail(SDK_EINVAL, "posterior_step: noise may be NULL only where nonzero == 0");
+  const bool vec = aligned16(a->x) && aligned16(a->model_out) && aligned16(a->noise) && aligned16(a->x_recon_in) &&
+                   aligned16(a->x_prev) && aligned16(a->x_recon);
+  const int64_t n4 = vec ? a->n / 4 : 0;
+  const int64_t items = std::max<int64_t>(n4, a->n - 4 * n4);
+  const int blocks = (int)std::min<int64_t>((items + 255) / 256, 2048);
+  hipLaunchKernelGGL(posterior_step_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a, n4);
+  return check_launch("posterior_step");
+}
+
+extern "C" int sdk_masked_q_sample(const sdk_masked_q_args* a, sdk_stream_t stream) {
+  if (!a || !a->x0 || !a->noise || !a->mask || !a->img || !a->out) return fail(SDK_EINVAL, "masked_q_sample: null pointer");
+  if (a->n <= 0 || a->hw <= 0 || a->per_sample <= 0 || a->per_sample % a->hw || a->n % a->per_sample ||
+      a->mask_mode < 0 || a->mask_mode > 2)
+    return fail(SDK_EINVAL, "masked_q_sample: bad geometry (n = batch * per_sample, per_sample = channels * hw)");
+  const bool vec = aligned16(a->x0) && aligned16(a->noise) && aligned16(a->img) && aligned16(a->out);
+  const int64_t n4 = vec ? a->n / 4 : 0;
+  const int64_t items = std::max<int64_t>(n4, a->n - 4 * n4);
+  const int blocks = (int)std::min<int64_t>((items + 255) / 256, 2048);
+  hipLaunchKernelGGL(masked_q_sample_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a, n4);
+  return check_launch("masked_q_sample");
+}
+
+extern "C" int sdk_concat_nchw_to_nhwc(const sdk_concat_args* a, sdk_stream_t stream) {
+  if (!a || !a->y || a->nsrc < 1 || a->nsrc > 4 || a->batch <= 0 || a->hw <= 0)
+    return fail(SDK_EINVAL, "concat_nchw_to_nhwc: bad args (1..4 sources)");
+  int64_t csum = 0;
+  for (int s = 0; s < a->nsrc; ++s) {
+    if (!a->src[s] || a->channels[s] <= 0) return fail(SDK_EINVAL, "concat_nchw_to_nhwc: null source / channels <= 0");
+    csum += a->channels[s];
+  }
+  if (a->c_pad < csum) return fail(SDK_EINVAL, "concat_nchw_to_nhwc: c_pad below the channel sum");
+  const int ngrp = (a->c_pad % 8 == 0 && aligned16(a->y)) ? a->c_pad / 8 : 0;
+  const int64_t bhw = (int64_t)a->batch * a->hw;
+  const int64_t nvec = ngrp * bhw, nscal = (a->c_pad - 8 * ngrp) * bhw;
+  const int blocks = (int)std::min<int64_t>((std::max(nvec, nscal) + 255) / 256, 2048);
+  hipLaunchKernelGGL(concat_nchw_to_nhwc_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a, ngrp, nvec,
+                     nscal);
+  return check_launch("concat_nchw_to_nhwc");
 }
 
 extern "C" const char* sdk_last_error(void) { return g_last_error.c_str(); }

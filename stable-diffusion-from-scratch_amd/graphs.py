@@ -1,8 +1,9 @@
 """HIP-graph replay of the UNet forward (one sampler step's ~600 kernel launches).
 
-``GraphedUNet(unet)(x, timesteps, context)`` captures ``unet.forward`` once per
-(input shapes, context tensor) and afterwards replays it: the inputs are copied into
-the graph's static buffers, the whole step is one ``hipGraphLaunch``.  Everything the
+``GraphedUNet(unet)(x, timesteps, context, concat)`` captures ``unet.forward`` once per
+(input shapes, context tensor, concat shapes) and afterwards replays it: the inputs (x, timesteps
+and the concat tensors of a 'concat' / 'hybrid' model) are copied into the graph's static
+buffers, the whole step is one ``hipGraphLaunch``.  Everything the
 forward launches goes through the C ABI on the current stream, so it is captured like
 any torch op.
 
@@ -43,9 +44,9 @@ class GraphedUNet:
         self._gen = getattr(unet, "prepare_generation", None)
 
     @staticmethod
-    def _key(x, timesteps, context):
+    def _key(x, timesteps, context, concat=()):
         ctx = None if context is None else (id(context), tuple(context.shape), context.dtype)
-        return tuple(x.shape), x.dtype, tuple(timesteps.shape), ctx
+        return tuple(x.shape), x.dtype, tuple(timesteps.shape), ctx, tuple(tuple(c.shape) for c in concat)
 
     def _valid(self, ent, context):
         if context is None:
@@ -53,12 +54,16 @@ class GraphedUNet:
         return ent["ctx"] is context and ent["ctx_version"] == context._version
 
     @torch.no_grad()
-    def __call__(self, x, timesteps, context=None):
+    def __call__(self, x, timesteps, context=None, concat=None):
+        # concat tensors (UNetModel.forward's extension) are inputs like x: shapes in the key, contents
+        # copied into static fp32 buffers on every replay (no identity cache, they change per call)
+        concat = [] if concat is None else [c.to(device=x.device, dtype=torch.float32) for c in concat]
+        kw = lambda cc: {"concat": cc} if cc else {}      # noqa: E731
         gen = getattr(self.unet, "prepare_generation", None)
         if gen != self._gen:
             self.reset()
             self._gen = gen
-        key = self._key(x, timesteps, context)
+        key = self._key(x, timesteps, context, concat)
         ent = self.graphs.get(key)
         if ent is not None and not self._valid(ent, context):
             del self.graphs[key]
@@ -67,18 +72,19 @@ class GraphedUNet:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("GraphedUNet: nested capture")
             sx, st = x.clone(), timesteps.clone()
+            sc = [c.clone() for c in concat]
             side = torch.cuda.Stream(device=x.device)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):          # settle caches/attributes outside the capture
-                self.unet(sx, st, context=context)
+                self.unet(sx, st, context=context, **kw(sc))
             torch.cuda.current_stream().wait_stream(side)
             kv = None
             if context is not None and hasattr(self.unet, "_context_kv"):
                 kv = self.unet._context_kv(context)[0]     # the K/V the capture will read (cache hit)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                out = self.unet(sx, st, context=context)
-            ent = {"graph": g, "x": sx, "t": st, "out": out, "ctx": context,
+                out = self.unet(sx, st, context=context, **kw(sc))
+            ent = {"graph": g, "x": sx, "t": st, "concat": sc, "out": out, "ctx": context,
                    "ctx_version": None if context is None else context._version, "kv": kv}
             self.graphs[key] = ent
             while len(self.graphs) > self.MAX_GRAPHS:
@@ -86,6 +92,8 @@ class GraphedUNet:
         self.graphs.move_to_end(key)
         ent["x"].copy_(x)
         ent["t"].copy_(timesteps)
+        for dst, src in zip(ent["concat"], concat):
+            dst.copy_(src)
         ent["graph"].replay()
         return ent["out"] if self.alias_output else ent["out"].clone()
 

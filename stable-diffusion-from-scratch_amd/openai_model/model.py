@@ -353,8 +353,24 @@ class UNetModel(nn.Module):
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
-    def forward(self, x, timesteps=None, context=None, y=None, **kwargs):
+    def forward(self, x, timesteps=None, context=None, y=None, concat=None, **kwargs):
+        """``concat`` (extension, not in the reference's signature): a list of up to three NCHW tensors
+        whose channels follow ``x``'s, i.e. the result of ``forward(torch.cat([x] + concat, 1), ...)``
+        (``DiffusionWrapper.forward`` 'concat' / 'hybrid', ``Diffusion/ddpm.py:51-63``) with the concat
+        folded into the NCHW → NHWC pack of the input, so the concatenated tensor is never built."""
         assert (y is not None) == (self.num_classes is not None), "y iff class-conditional"
+        concat = list(concat) if concat is not None else []
+        if concat:
+            if len(concat) > 3:
+                raise ValueError(f"sd_amd.UNetModel: at most 3 concat tensors, got {len(concat)}")
+            for c in concat:
+                if not torch.is_tensor(c) or c.dim() != 4 or c.shape[0] != x.shape[0] or c.shape[2:] != x.shape[2:]:
+                    raise ValueError("sd_amd.UNetModel: concat tensors must be NCHW with x's batch and spatial "
+                                     f"size {tuple(x.shape)}, got {tuple(getattr(c, 'shape', ()))}")
+            csum = x.shape[1] + sum(c.shape[1] for c in concat)
+            if csum != self.in_channels:
+                raise ValueError(f"sd_amd.UNetModel: x and concat carry {csum} channels, in_channels is "
+                                 f"{self.in_channels}")
         if not x.is_cuda:
             raise TypeError("sd_amd.UNetModel: HIP path only — move inputs to the GPU")
         if self._prepared_on != x.device:
@@ -377,7 +393,11 @@ class UNetModel(nn.Module):
         emb_all = ops.linear(self._pc_emb, emb, silu=True, out_mode=ops.OUT_ROWS_F32)
         kv, Lc = self._context_kv(context)
         st = {"emb": emb_all, "kv": kv, "Lc": Lc}
-        h = ops.nchw_to_nhwc(x.float(), self._cin_pad)
+        if concat:
+            h = ops.concat_nchw_to_nhwc([x.float()] + [c.to(device=x.device, dtype=torch.float32) for c in concat],
+                                        self._cin_pad)
+        else:
+            h = ops.nchw_to_nhwc(x.float(), self._cin_pad)
         hs = []
         for module in self.input_blocks:
             h = module._run(h, st)

@@ -1170,6 +1170,116 @@ def ddim_xprev(pred_x0, e, sc: dict, x=None, noise=None, e_uncond=None, guidance
     return xp
 
 
+# --------------------------------------------------------------------------- ancestral sampler / concat
+
+def concat_nchw_to_nhwc(srcs, c_pad: int):
+    """``nchw_to_nhwc(torch.cat(srcs, 1), c_pad)`` in one pass, without the concatenated fp32 tensor:
+    1..4 NCHW fp32 sources of one ``B, H, W`` → NHWC fp16 ``[B, H, W, c_pad]`` (zeros past the channel sum)."""
+    srcs = list(srcs)
+    if not 1 <= len(srcs) <= 4:
+        raise ValueError(f"sd_amd.concat_nchw_to_nhwc: 1..4 sources, got {len(srcs)}")
+    for s in srcs:
+        _need_cuda(s, "concat_nchw_to_nhwc", torch.float32)
+        if s.dim() != 4 or s.shape[0] != srcs[0].shape[0] or s.shape[2:] != srcs[0].shape[2:]:
+            raise ValueError("sd_amd.concat_nchw_to_nhwc: sources must be NCHW with the same batch and spatial "
+                             f"size, got {[tuple(t.shape) for t in srcs]}")
+    srcs = [s.contiguous() for s in srcs]
+    B, _, H, W = srcs[0].shape
+    csum = sum(s.shape[1] for s in srcs)
+    if c_pad < csum:
+        raise ValueError(f"sd_amd.concat_nchw_to_nhwc: c_pad {c_pad} below the channel sum {csum}")
+    y = torch.empty(B, H, W, c_pad, dtype=torch.float16, device=srcs[0].device)
+    a = _lib.ConcatArgs()
+    for i, s in enumerate(srcs):
+        a.src[i], a.channels[i] = s.data_ptr(), s.shape[1]
+    a.nsrc, a.y, a.batch, a.hw, a.c_pad = len(srcs), y.data_ptr(), B, H * W, c_pad
+    check(lib().sdk_concat_nchw_to_nhwc(C.byref(a), _stream()), "concat_nchw_to_nhwc")
+    return y
+
+
+def _t_runs(t, batch):
+    """``t`` (an int, or one int per sample) → [(first sample, end sample, t)] runs of equal t."""
+    ts = [int(t)] * batch if not isinstance(t, (list, tuple)) else [int(v) for v in t]
+    if len(ts) != batch:
+        raise ValueError(f"sd_amd: {len(ts)} timesteps for a batch of {batch}")
+    runs, b0 = [], 0
+    for b in range(1, batch + 1):
+        if b == batch or ts[b] != ts[b0]:
+            runs.append((b0, b, ts[b0]))
+            b0 = b
+    return runs
+
+
+def posterior_step(x, model_out, t, tables: dict, noise=None, *, x0_param=False, clip=False, temperature=1.0,
+                   stage=0, x_recon_in=None, x_prev=None, x_recon=None, want_x_recon=False):
+    """Fused ancestral step of ``LatentDiffusion.p_sample`` (see ``sdk_posterior_step``).  ``t``: a host
+    int or one per sample (a launch per run of equal t); ``tables``: host fp32 arrays
+    ``c_recip, c_recipm1, coef1, coef2, sigma`` indexed by t.  ``stage`` 0: x_prev (and x_recon when
+    ``want_x_recon``); 1: x_recon only; 2: x_prev from ``x_recon_in``.  Returns (x_prev, x_recon)."""
+    ref = x if x is not None else model_out
+    B = ref.shape[0]
+    ins = {"x": x, "model_out": model_out, "noise": noise, "x_recon_in": x_recon_in}
+    for k, v in ins.items():
+        if v is not None:
+            _need_cuda(v, "posterior_step " + k, torch.float32)
+            if v.shape != ref.shape:
+                raise ValueError(f"sd_amd.posterior_step: {k} {tuple(v.shape)} vs {tuple(ref.shape)}")
+            ins[k] = v.contiguous()
+    if stage != 1 and x_prev is None:
+        x_prev = torch.empty_like(ref, memory_format=torch.contiguous_format)
+    if (stage == 1 or want_x_recon) and x_recon is None:
+        x_recon = torch.empty_like(ref, memory_format=torch.contiguous_format)
+    per = ref.numel() // B
+    a = _lib.PosteriorArgs()
+    a.stage, a.x0_param, a.clip, a.temperature = int(stage), int(bool(x0_param)), int(bool(clip)), float(temperature)
+    for b0, b1, ti in _t_runs(t, B):
+        off = b0 * per * 4
+        for k, v in ins.items():
+            setattr(a, k, v.data_ptr() + off if v is not None else None)
+        a.x_prev = x_prev.data_ptr() + off if x_prev is not None and stage != 1 else None
+        a.x_recon = x_recon.data_ptr() + off if x_recon is not None else None
+        a.n = (b1 - b0) * per
+        a.c_recip, a.c_recipm1 = float(tables["c_recip"][ti]), float(tables["c_recipm1"][ti])
+        a.coef1, a.coef2, a.sigma = float(tables["coef1"][ti]), float(tables["coef2"][ti]), float(tables["sigma"][ti])
+        a.nonzero = 0.0 if ti == 0 or noise is None else 1.0      # no noise: x_prev is the posterior mean
+        check(lib().sdk_posterior_step(C.byref(a), _stream()), "posterior_step")
+    return x_prev, x_recon
+
+
+def masked_q_sample(x0, noise, mask, img, t, sqrt_acp, sqrt_1m_acp, out=None):
+    """``(sqrt_acp[t]·x0 + sqrt_1m_acp[t]·noise)·mask + (1 − mask)·img`` (``ldm/diffusion/ddpm.py:1783-1784``),
+    the mask ``[B,1,H,W]``, ``[1,1,H,W]`` or ``[B,C,H,W]`` broadcast by index.  ``t`` as in
+    ``posterior_step``; the tables are host fp32 arrays.  ``out=img`` updates in place."""
+    for k, v in (("x0", x0), ("noise", noise), ("mask", mask), ("img", img)):
+        _need_cuda(v, "masked_q_sample " + k, torch.float32)
+    if x0.dim() != 4 or noise.shape != x0.shape or img.shape != x0.shape:
+        raise ValueError("sd_amd.masked_q_sample: x0, noise and img must be one NCHW shape")
+    B, Cc, H, W = x0.shape
+    modes = {(B, 1, H, W): 0, (1, 1, H, W): 1, (B, Cc, H, W): 2}      # equal shapes index alike
+    if tuple(mask.shape) not in modes:
+        raise ValueError(f"sd_amd.masked_q_sample: mask {tuple(mask.shape)} does not broadcast over {tuple(x0.shape)}")
+    mode = modes[tuple(mask.shape)]
+    x0, noise, mask = x0.contiguous(), noise.contiguous(), mask.contiguous()
+    if not img.is_contiguous():
+        if out is img:
+            raise ValueError("sd_amd.masked_q_sample: in-place update needs a contiguous img")
+        img = img.contiguous()
+    y = out if out is not None else torch.empty_like(img)
+    if y.shape != img.shape or not y.is_contiguous() or y.dtype != torch.float32:
+        raise ValueError("sd_amd.masked_q_sample: out must be a contiguous fp32 tensor of img's shape")
+    per, hw = Cc * H * W, H * W
+    a = _lib.MaskedQArgs()
+    a.per_sample, a.hw, a.mask_mode = per, hw, mode
+    for b0, b1, ti in _t_runs(t, B):
+        off = b0 * per * 4
+        a.x0, a.noise, a.img, a.out = x0.data_ptr() + off, noise.data_ptr() + off, img.data_ptr() + off, y.data_ptr() + off
+        a.mask = mask.data_ptr() + (0 if mode == 1 else b0 * (hw if mode == 0 else per) * 4)
+        a.n = (b1 - b0) * per
+        a.sqrt_acp, a.sqrt_1m_acp = float(sqrt_acp[ti]), float(sqrt_1m_acp[ti])
+        check(lib().sdk_masked_q_sample(C.byref(a), _stream()), "masked_q_sample")
+    return y
+
+
 # --------------------------------------------------------------------------- vector quantiser
 
 def _vq_codebook(codebook, what):
