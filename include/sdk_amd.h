@@ -502,6 +502,38 @@ int sdk_gelu(const void* x, void* y, int64_t n, sdk_stream_t stream);
 int sdk_upsample_nearest2x_padded(const void* x, int32_t ld_x, void* y, int32_t batch, int32_t h, int32_t w,
                                   int32_t channels, int32_t pad, sdk_stream_t stream);
 
+/* ---------------------------------------------------------------- ADM ("guided diffusion") UNet options
+ * GroupNorm with FiLM conditioning (+ SiLU), the `use_scale_shift_norm` ResBlock (openai_model/model.py:244-248:
+ * out_norm(h) * (1 + scale) + shift, then SiLU): as sdk_group_norm, with film = fp32 [batch][film_ld], the
+ * scale at film[b*film_ld + film_off + c] and the shift at film[b*film_ld + film_off + channels + c] (this
+ * block's columns of the batched emb_layers GEMM).  The FiLM terms are folded into the per-(batch, channel)
+ * affine in fp32 (s' = s*(1+f), t' = t*(1+f) + g) before the apply pass, so x is still read once and y written
+ * once.  Statistics from part0 / part1 or a statistics pass, then the fold, then the apply pass at every level;
+ * a->scale / a->shift are required and hold the folded affine afterwards. */
+int sdk_group_norm_film(const sdk_group_norm_args* a, const float* film, int32_t film_ld, int32_t film_off,
+                        int32_t silu, void* y, int32_t ld_y, int32_t h, int32_t w, int32_t pad, const float* part0,
+                        int32_t nch0, const float* part1, int32_t nch1, sdk_stream_t stream);
+
+/* GroupNorm apply (+ SiLU) + 2x resample with two outputs from one read of x — the resampling ResBlock
+ * (`resblock_updown`, openai_model/model.py:233-238: h = h_upd(SiLU(GN(x))), x = x_upd(x)) and, with
+ * a->scale == NULL, the stand-alone Downsample / Upsample of `conv_resample=False` (:91-97, :119-131).
+ * mode: SDK_RESAMPLE_AVGPOOL2 = F.avg_pool2d(., 2) (odd h / w floor), SDK_RESAMPLE_NEAREST2 = nearest x2.
+ * x = a->src0 (| a->src1 as a 2-source concat) [batch][h][w], a->scale / a->shift the per-(batch, channel)
+ * affine (sdk_group_norm_finalize).  y_act = resample(silu?(x*scale + shift)) in a zero-bordered
+ * [batch][ho+2pad][wo+2pad][channels] image (pooling averages the four activated values in fp32, rounded to
+ * fp16 once); y_raw = resample(x), contiguous [batch][ho][wo][channels].  Either output may be NULL; y_act
+ * needs the affine.  channels % 8 == 0 (else SDK_EINVAL), channels <= 4096. */
+enum { SDK_RESAMPLE_AVGPOOL2 = 0, SDK_RESAMPLE_NEAREST2 = 1 };
+int sdk_group_norm_resample(const sdk_group_norm_args* a, int32_t mode, int32_t silu, int32_t h, int32_t w,
+                            int32_t pad, void* y_act, void* y_raw, sdk_stream_t stream);
+
+/* Class-label embedding add (openai_model/model.py:568-570: emb = emb + label_emb(y)):
+ * out[b][:] = fp16(float(emb[b][:]) + table[ids[b]][:]); emb / out fp16 [batch][dim], table fp32 [n][dim],
+ * ids int64 [batch], dim % 8 == 0.  The table is never read outside [0, n): an id out of range writes NaN
+ * into that whole row of out. */
+int sdk_embedding_add(const void* emb, const float* table, const int64_t* ids, void* out, int32_t batch, int32_t dim,
+                      int32_t n, sdk_stream_t stream);
+
 /* ---------------------------------------------------------------- introspection */
 const char* sdk_last_error(void);
 int sdk_version(void);

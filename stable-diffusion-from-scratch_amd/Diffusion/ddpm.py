@@ -3,7 +3,8 @@
 Kept: ``register_schedule`` buffers (``ddpm.py:195-253``), ``apply_model``
 conditioning wrapping (``ddpm.py:1139-1147,1269-1272`` → ``{'c_crossattn': [c]}``),
 ``DiffusionWrapper.forward`` dispatch (``ddpm.py:46-73``: None, 'crossattn', 'concat' and 'hybrid' — the
-channel concat is folded into the UNet's input pack; 'adm' raises, the UNet has no class head),
+channel concat is folded into the UNet's input pack; 'adm' passes ``y = c_crossattn[0]`` to a UNet with a
+class head, ``num_classes``, and raises for one without),
 LatentDiffusion's ancestral sampler (``ldm/diffusion/ddpm.py:1528-1811``: ``q_sample`` …
 ``p_sample_loop`` / ``sample`` with ``clip_denoised``, ``quantize_denoised``, ``mask`` / ``x0``), ``decode_first_stage``
 with the CompVis scaling ``z / scale_factor`` (``ldm/diffusion/ddpm.py:1095``;
@@ -61,9 +62,11 @@ class DiffusionWrapper(nn.Module):
                 raise ValueError("sd_amd: timesteps must be integral")
         return t.to(device=device, dtype=torch.long)
 
-    def _unet(self, x, t, context=None, concat=None):
+    def _unet(self, x, t, context=None, concat=None, y=None):
         t = self._int_timesteps(t, x.device)
         kw = {"concat": list(concat)} if concat else {}
+        if y is not None:
+            kw["y"] = y
         if self._graphs_on:
             return self._graphed(x, t.reshape(-1).expand(x.shape[0]), context, **kw)
         return self.diffusion_model(x, t, context=context, **kw)
@@ -84,8 +87,13 @@ class DiffusionWrapper(nn.Module):
                     raise ValueError("sd_amd: conditioning_key=hybrid needs c_crossattn")
                 cc = c_crossattn[0] if len(c_crossattn) == 1 else torch.cat(c_crossattn, 1)
             return self._unet(x, t, context=cc, concat=c_concat)
-        raise NotImplementedError(f"sd_amd: conditioning_key={self.conditioning_key} needs a class-conditional "
-                                  "UNet (no class head in this UNetModel)")
+        if getattr(self.diffusion_model, "num_classes", None) is None:
+            raise NotImplementedError(f"sd_amd: conditioning_key={self.conditioning_key} needs a class-conditional "
+                                      "UNet (this one has no class head: num_classes is None)")
+        # Diffusion/ddpm.py:65-67: the class labels travel as c_crossattn[0]
+        if not c_crossattn:
+            raise ValueError("sd_amd: conditioning_key=adm needs c_crossattn=[y]")
+        return self._unet(x, t, y=c_crossattn[0])
 
 
 def _is_vq(first_stage):

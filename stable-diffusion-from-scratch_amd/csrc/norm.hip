@@ -725,6 +725,140 @@ __global__ void __launch_bounds__(256) upsample_nearest2x_pad_kernel(const half_
   }
 }
 
+// FiLM ("scale-shift norm", reference openai_model/model.py:244-248: out_norm(h) * (1 + scale) + shift) folded
+// into the per-(batch, channel) GroupNorm affine before the apply pass: with y = x*s + t the conditioned value
+// is x*(s*(1+f)) + (t*(1+f) + g), so the activation is still read once and written once.  f = film[b][off + c],
+// g = film[b][off + channels + c]; O(batch * channels) work, in place.
+__global__ void __launch_bounds__(256) gn_film_fold_kernel(float* scale, float* shift, const float* film, int ld,
+                                                           int off, int channels, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int b = i / channels, c = i - b * channels;
+  const float* fr = film + (size_t)b * ld + off;
+  const float k = 1.0f + fr[c];
+  scale[i] = scale[i] * k;
+  shift[i] = shift[i] * k + fr[channels + c];
+}
+
+// GroupNorm apply + SiLU + 2x resample with two outputs from ONE read of x (the resampling ResBlock of
+// reference openai_model/model.py:233-238: h = h_upd(SiLU(GN(x))), x = x_upd(x)).  DOWN: avg-pool 2x2 stride 2
+// (odd h / w floor: the last row / column is dropped, as F.avg_pool2d does), else nearest x2.  y_act = the
+// resampled activation in a zero-bordered [B][ho+2pad][wo+2pad][C] image (pooling averages the four ACTIVATED
+// values in fp32 and rounds once), y_raw = the resampled x itself, contiguous [B][ho][wo][C]; either may be NULL
+// (scale == NULL: y_raw only, the stand-alone Downsample / Upsample without a conv).  Grid (padded output row,
+// image) as upsample_nearest2x_pad_kernel; the image's scale / shift staged in LDS once; every load of a thread's
+// RS elements is issued before its first store.
+template <bool DOWN>
+__global__ void __launch_bounds__(256) gn_resample_kernel(const half_t* s0, const half_t* s1, int c_split, int ld0,
+                                                          int ld1, int h, int w, int pad, int channels,
+                                                          const float* scale, const float* shift, int silu,
+                                                          half_t* y_act, half_t* y_raw, unsigned divm) {
+  extern __shared__ __attribute__((aligned(16))) float gst[];   // [channels] scale | [channels] shift
+  constexpr int NL = DOWN ? 4 : 1, RS = DOWN ? 2 : 4;           // loads per output element, elements per thread
+  const int tid = threadIdx.x, py = blockIdx.x, b = blockIdx.y;
+  const int c8 = channels / 8;
+  const int ho = DOWN ? h / 2 : 2 * h, wo = DOWN ? w / 2 : 2 * w, hp = ho + 2 * pad, wp = wo + 2 * pad;
+  const bool act = y_act != nullptr;
+  if (act) {
+    for (int e = tid; e < channels / 4; e += 256) {
+      reinterpret_cast<f4*>(gst)[e] = reinterpret_cast<const f4*>(scale + (size_t)b * channels)[e];
+      reinterpret_cast<f4*>(gst + channels)[e] = reinterpret_cast<const f4*>(shift + (size_t)b * channels)[e];
+    }
+    __syncthreads();
+  }
+  const int oy = py - pad;
+  const bool row_in = (unsigned)oy < (unsigned)ho;
+  const int n = wp * c8;
+  half_t* arow = act ? y_act + ((size_t)b * hp + py) * wp * (size_t)channels : nullptr;
+  if (!row_in) {                                                 // a border row of y_act (pad > 0 only with y_act)
+    for (int i = tid; i < n; i += 256) *reinterpret_cast<h8*>(arow + (size_t)i * 8) = h8{};
+    return;
+  }
+  half_t* rrow = y_raw ? y_raw + ((size_t)b * ho + oy) * wo * (size_t)channels : nullptr;
+  const size_t src0 = ((size_t)b * h + (DOWN ? 2 * oy : oy >> 1)) * w;
+  for (int i0 = tid; i0 < n; i0 += 256 * RS) {
+    h8 v[RS][NL];
+    int px[RS], cc[RS];
+    bool in[RS];
+#pragma unroll
+    for (int u = 0; u < RS; ++u) {
+      const int i = i0 + 256 * u;
+      px[u] = (int)(((unsigned long long)(unsigned)i * divm) >> 32);
+      cc[u] = (i - px[u] * c8) * 8;
+      const int ox = px[u] - pad;
+      in[u] = i < n && (unsigned)ox < (unsigned)wo;
+      if constexpr (DOWN) {
+#pragma unroll
+        for (int k = 0; k < NL; ++k)
+          v[u][k] = in[u] ? load_px(s0, s1, c_split, ld0, ld1, src0 + (size_t)(k >> 1) * w + 2 * ox + (k & 1), cc[u])
+                          : h8{};
+      } else {
+        v[u][0] = in[u] ? load_px(s0, s1, c_split, ld0, ld1, src0 + (ox >> 1), cc[u]) : h8{};
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < RS; ++u) {
+      if (i0 + 256 * u >= n) break;
+      h8 oa = {}, orw = {};
+      if (in[u]) {
+        if (act) {
+          const f4* ps = reinterpret_cast<const f4*>(gst + cc[u]);
+          const f4* pt = reinterpret_cast<const f4*>(gst + channels + cc[u]);
+          const f4 sa = ps[0], sb = ps[1], ta = pt[0], tb = pt[1];
+          const float sc[8] = {sa[0], sa[1], sa[2], sa[3], sb[0], sb[1], sb[2], sb[3]};
+          const float sh[8] = {ta[0], ta[1], ta[2], ta[3], tb[0], tb[1], tb[2], tb[3]};
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            float acc = 0.f;
+#pragma unroll
+            for (int k = 0; k < NL; ++k) {
+              float x = (float)v[u][k][j] * sc[j] + sh[j];
+              if (silu) x = x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
+              acc += x;
+            }
+            oa[j] = (half_t)(DOWN ? acc * 0.25f : acc);
+          }
+        }
+        if constexpr (DOWN) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            orw[j] = (half_t)((((float)v[u][0][j] + (float)v[u][1][j]) + ((float)v[u][2][j] + (float)v[u][3][j])) *
+                              0.25f);
+        } else {
+          orw = v[u][0];
+        }
+      }
+      if (act) *reinterpret_cast<h8*>(arow + (size_t)px[u] * channels + cc[u]) = oa;
+      if (rrow && in[u]) *reinterpret_cast<h8*>(rrow + (size_t)(px[u] - pad) * channels + cc[u]) = orw;
+    }
+  }
+}
+
+// Class-label embedding add (reference openai_model/model.py:568-570: emb = emb + label_emb(y)):
+// out[b][:] = fp16(float(emb[b][:]) + table[ids[b]][:]), 8 values per thread.  The table is never read outside
+// [0, n): an id out of range writes NaN into its whole row.  Grid (ceil(dim / 8 / 256), batch).
+__global__ void __launch_bounds__(256) embedding_add_kernel(const half_t* emb, const float* table, const int64_t* ids,
+                                                            half_t* out, int dim, int n) {
+  const int v = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+  if (v >= dim / 8) return;
+  const int64_t id = ids[b];
+  const bool ok = id >= 0 && id < (int64_t)n;
+  const h8 e = *reinterpret_cast<const h8*>(emb + (size_t)b * dim + 8 * v);
+  f4 t0 = {}, t1 = {};
+  if (ok) {
+    const f4* tp = reinterpret_cast<const f4*>(table + (size_t)id * dim + 8 * v);
+    t0 = tp[0];
+    t1 = tp[1];
+  }
+  h8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float s = (float)e[j] + (j < 4 ? t0[j & 3] : t1[j & 3]);
+    o[j] = (half_t)(ok ? s : __builtin_nanf(""));
+  }
+  *reinterpret_cast<h8*>(out + (size_t)b * dim + 8 * v) = o;
+}
+
 // ceil(2^32 / d) when i * that >> 32 == i / d for every i < n (a closed-form bound), else 0
 unsigned pad_row_divm(int n, int d) {
   // m = ceil(2^32 / d) = (2^32 + e) / d with 0 <= e < d, so i * m / 2^32 = i / d + i * e / (d * 2^32): the
@@ -1131,4 +1265,83 @@ extern "C" int sdk_upsample_nearest2x_padded(const void* x, int32_t ld_x, void* 
   hipLaunchKernelGGL(upsample_nearest2x_pad_kernel, dim3(hp, batch), dim3(256), 0, (hipStream_t)stream,
                      (const half_t*)x, ld_x, h, w, pad, channels, (half_t*)y, divm);
   return check_launch("upsample_nearest2x_padded");
+}
+
+// GroupNorm with FiLM conditioning (+ SiLU) in one C call: the statistics as sdk_group_norm_finalize (the
+// producers' partials, else a statistics pass), the FiLM fold over [batch][channels], then the apply pass — at
+// every level, the small ones included (the single-launch forms of sdk_group_norm keep their affine in LDS, so
+// they have nowhere to fold it).  a->scale / a->shift hold the FOLDED affine afterwards.
+extern "C" int sdk_group_norm_film(const sdk_group_norm_args* a, const float* film, int32_t film_ld, int32_t film_off,
+                                   int32_t silu, void* y, int32_t ld_y, int32_t h, int32_t w, int32_t pad,
+                                   const float* part0, int32_t nch0, const float* part1, int32_t nch1,
+                                   sdk_stream_t stream) {
+  if (!a || !a->src0 || !y || !a->scale || !a->shift || !film)
+    return fail(SDK_EINVAL, "group_norm_film: null pointer (scale / shift buffers are required)");
+  if (a->channels <= 0 || a->channels % 8 || a->groups <= 0 || a->channels % a->groups || a->c_split % 8 ||
+      a->c_split <= 0 || a->c_split > a->channels || ld_y % 8 || ld_y < a->channels)
+    return fail(SDK_EINVAL, "group_norm_film: channels/c_split/ld_y must be multiples of 8, channels % groups == 0");
+  if (film_off < 0 || film_ld < film_off + 2 * a->channels)
+    return fail(SDK_EINVAL, "group_norm_film: film rows hold 2*channels values from film_off");
+  if (h <= 0 || w <= 0 || (int64_t)h * w != a->hw || pad < 0 || pad > 4)
+    return fail(SDK_EINVAL, "group_norm_film: h*w must equal hw, pad in [0, 4]");
+  if (a->batch <= 0) return SDK_OK;
+  if ((int64_t)a->batch * a->channels >= (1LL << 31)) return fail(SDK_EINVAL, "group_norm_film: batch*channels");
+  if (int e = sdk_group_norm_finalize(a, part0, nch0, part1, nch1, stream)) return e;
+  const int n = a->batch * a->channels;
+  hipLaunchKernelGGL(gn_film_fold_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a->scale, a->shift,
+                     film, film_ld, film_off, a->channels, n);
+  if (int e = check_launch("gn_film_fold")) return e;
+  return pad ? sdk_group_norm_apply_padded(a, silu, y, ld_y, h, w, pad, stream)
+             : sdk_group_norm_apply(a, silu, y, ld_y, stream);
+}
+
+extern "C" int sdk_group_norm_resample(const sdk_group_norm_args* a, int32_t mode, int32_t silu, int32_t h, int32_t w,
+                                       int32_t pad, void* y_act, void* y_raw, sdk_stream_t stream) {
+  if (!a || !a->src0 || (!y_act && !y_raw)) return fail(SDK_EINVAL, "group_norm_resample: null pointer");
+  if (mode != SDK_RESAMPLE_AVGPOOL2 && mode != SDK_RESAMPLE_NEAREST2)
+    return fail(SDK_EINVAL, "group_norm_resample: mode");
+  if (a->channels <= 0 || a->channels % 8 || a->channels > 4096 || a->c_split % 8 || a->c_split <= 0 ||
+      a->c_split > a->channels)
+    return fail(SDK_EINVAL, "group_norm_resample: channels/c_split must be multiples of 8, channels <= 4096");
+  if (a->c_split < a->channels && !a->src1) return fail(SDK_EINVAL, "group_norm_resample: concat without src1");
+  if (a->ld0 % 8 || a->ld0 < a->c_split ||
+      (a->c_split < a->channels && (a->ld1 % 8 || a->ld1 < a->channels - a->c_split)))
+    return fail(SDK_EINVAL, "group_norm_resample: ld % 8");
+  if (y_act && (!a->scale || !a->shift))
+    return fail(SDK_EINVAL, "group_norm_resample: the activated output needs scale / shift");
+  if (a->batch <= 0 || h <= 0 || w <= 0 || (int64_t)h * w != a->hw || pad < 0 || pad > 4)
+    return fail(SDK_EINVAL, "group_norm_resample: h*w must equal hw, pad in [0, 4]");
+  const bool down = mode == SDK_RESAMPLE_AVGPOOL2;
+  if (down && (h < 2 || w < 2)) return fail(SDK_EINVAL, "group_norm_resample: pooling needs h, w >= 2");
+  if (!y_act) pad = 0;
+  const int c8 = a->channels / 8;
+  const int64_t ho = down ? h / 2 : 2 * (int64_t)h, wo = down ? w / 2 : 2 * (int64_t)w;
+  const int64_t hp = ho + 2 * pad, wp = wo + 2 * pad;
+  if (hp > 65535 || a->batch > 65535 || wp * c8 >= (1 << 24))
+    return fail(SDK_EINVAL, "group_norm_resample: image too large");
+  const unsigned divm = pad_row_divm((int)(wp * c8) + 256 * 4, c8);
+  if (!divm) return fail(SDK_EINVAL, "group_norm_resample: no exact row split");
+  const size_t lds = y_act ? (size_t)a->channels * 8 : 0;
+  if (down)
+    hipLaunchKernelGGL(gn_resample_kernel<true>, dim3((unsigned)hp, a->batch), dim3(256), lds, (hipStream_t)stream,
+                       (const half_t*)a->src0, (const half_t*)a->src1, a->c_split, a->ld0, a->ld1, h, w, pad,
+                       a->channels, a->scale, a->shift, silu, (half_t*)y_act, (half_t*)y_raw, divm);
+  else
+    hipLaunchKernelGGL(gn_resample_kernel<false>, dim3((unsigned)hp, a->batch), dim3(256), lds, (hipStream_t)stream,
+                       (const half_t*)a->src0, (const half_t*)a->src1, a->c_split, a->ld0, a->ld1, h, w, pad,
+                       a->channels, a->scale, a->shift, silu, (half_t*)y_act, (half_t*)y_raw, divm);
+  return check_launch("gn_resample");
+}
+
+extern "C" int sdk_embedding_add(const void* emb, const float* table, const int64_t* ids, void* out, int32_t batch,
+                                 int32_t dim, int32_t n, sdk_stream_t stream) {
+  if (!emb || !table || !ids || !out || dim <= 0 || dim % 8 || n <= 0)
+    return fail(SDK_EINVAL, "embedding_add: bad args (dim must be a positive multiple of 8)");
+  if (((uintptr_t)emb | (uintptr_t)table | (uintptr_t)out) & 15)
+    return fail(SDK_EINVAL, "embedding_add: emb / table / out 16-B alignment");
+  if (batch <= 0) return SDK_OK;
+  if (batch > 65535) return fail(SDK_EINVAL, "embedding_add: batch > 65535");
+  hipLaunchKernelGGL(embedding_add_kernel, dim3((dim / 8 + 255) / 256, batch), dim3(256), 0, (hipStream_t)stream,
+                     (const half_t*)emb, table, ids, (half_t*)out, dim, n);
+  return check_launch("embedding_add");
 }

@@ -1,8 +1,8 @@
 """HIP-graph replay of the UNet forward (one sampler step's ~600 kernel launches).
 
-``GraphedUNet(unet)(x, timesteps, context, concat)`` captures ``unet.forward`` once per
-(input shapes, context tensor, concat shapes) and afterwards replays it: the inputs (x, timesteps
-and the concat tensors of a 'concat' / 'hybrid' model) are copied into the graph's static
+``GraphedUNet(unet)(x, timesteps, context, concat, y)`` captures ``unet.forward`` once per
+(input shapes, context tensor, concat shapes, label shape) and afterwards replays it: the inputs (x, timesteps,
+the class labels ``y`` of an 'adm' model and the concat tensors of a 'concat' / 'hybrid' model) are copied into the graph's static
 buffers, the whole step is one ``hipGraphLaunch``.  Everything the
 forward launches goes through the C ABI on the current stream, so it is captured like
 any torch op.
@@ -44,9 +44,10 @@ class GraphedUNet:
         self._gen = getattr(unet, "prepare_generation", None)
 
     @staticmethod
-    def _key(x, timesteps, context, concat=()):
+    def _key(x, timesteps, context, concat=(), y=None):
         ctx = None if context is None else (id(context), tuple(context.shape), context.dtype)
-        return tuple(x.shape), x.dtype, tuple(timesteps.shape), ctx, tuple(tuple(c.shape) for c in concat)
+        return (tuple(x.shape), x.dtype, tuple(timesteps.shape), ctx, tuple(tuple(c.shape) for c in concat),
+                None if y is None else tuple(y.shape))
 
     def _valid(self, ent, context):
         if context is None:
@@ -54,16 +55,20 @@ class GraphedUNet:
         return ent["ctx"] is context and ent["ctx_version"] == context._version
 
     @torch.no_grad()
-    def __call__(self, x, timesteps, context=None, concat=None):
+    def __call__(self, x, timesteps, context=None, concat=None, y=None):
         # concat tensors (UNetModel.forward's extension) are inputs like x: shapes in the key, contents
         # copied into static fp32 buffers on every replay (no identity cache, they change per call)
         concat = [] if concat is None else [c.to(device=x.device, dtype=torch.float32) for c in concat]
-        kw = lambda cc: {"concat": cc} if cc else {}      # noqa: E731
+        # class labels (y) are one more static input: int64 on the device, copied on every replay like timesteps
+        # (a device y is never range-checked on the host: an id out of range gives NaN rows, not a fault)
+        if y is not None:
+            y = torch.as_tensor(y).to(device=x.device, dtype=torch.int64)
+        kw = lambda cc, yy=None: dict({"concat": cc} if cc else {}, **({} if yy is None else {"y": yy}))  # noqa: E731
         gen = getattr(self.unet, "prepare_generation", None)
         if gen != self._gen:
             self.reset()
             self._gen = gen
-        key = self._key(x, timesteps, context, concat)
+        key = self._key(x, timesteps, context, concat, y)
         ent = self.graphs.get(key)
         if ent is not None and not self._valid(ent, context):
             del self.graphs[key]
@@ -73,18 +78,19 @@ class GraphedUNet:
                 raise RuntimeError("GraphedUNet: nested capture")
             sx, st = x.clone(), timesteps.clone()
             sc = [c.clone() for c in concat]
+            sy = None if y is None else y.clone()
             side = torch.cuda.Stream(device=x.device)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):          # settle caches/attributes outside the capture
-                self.unet(sx, st, context=context, **kw(sc))
+                self.unet(sx, st, context=context, **kw(sc, sy))
             torch.cuda.current_stream().wait_stream(side)
             kv = None
             if context is not None and hasattr(self.unet, "_context_kv"):
                 kv = self.unet._context_kv(context)[0]     # the K/V the capture will read (cache hit)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                out = self.unet(sx, st, context=context, **kw(sc))
-            ent = {"graph": g, "x": sx, "t": st, "concat": sc, "out": out, "ctx": context,
+                out = self.unet(sx, st, context=context, **kw(sc, sy))
+            ent = {"graph": g, "x": sx, "t": st, "concat": sc, "y": sy, "out": out, "ctx": context,
                    "ctx_version": None if context is None else context._version, "kv": kv}
             self.graphs[key] = ent
             while len(self.graphs) > self.MAX_GRAPHS:
@@ -94,6 +100,8 @@ class GraphedUNet:
         ent["t"].copy_(timesteps)
         for dst, src in zip(ent["concat"], concat):
             dst.copy_(src)
+        if y is not None:
+            ent["y"].copy_(y)
         ent["graph"].replay()
         return ent["out"] if self.alias_output else ent["out"].clone()
 

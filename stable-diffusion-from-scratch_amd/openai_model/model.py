@@ -14,6 +14,11 @@ every conv/linear/norm/attention runs in libsdk_amd.so:
   next block reads both tensors as one K range.
 * Upsample's nearest-x2 is folded into its conv's address generation.
 * All 22 ResBlock ``emb_layers`` projections run as ONE GEMM per step.
+* The ADM options: ``use_scale_shift_norm`` folds the FiLM (scale, shift) into the GroupNorm affine
+  (``ops.group_norm_film``: no extra pass over the activation); a resampling ResBlock (``resblock_updown``)
+  reads ``x`` once and writes both ``resample(SiLU(GN(x)))`` and ``resample(x)`` (``ops.group_norm_resample``),
+  whose raw half is also the avg-pool ``Downsample`` / conv-less ``Upsample`` of ``conv_resample=False``;
+  ``num_classes`` adds the ``label_emb`` row to the timestep embedding (``ops.embedding_add``).
 """
 from __future__ import annotations
 
@@ -24,7 +29,7 @@ from torch import nn
 
 from .. import ops
 from .attention import AttentionBlock, SpatialTransformer
-from .utils import conv_nd, linear, normalization, timestep_frequencies, zero_module
+from .utils import avg_pool_nd, conv_nd, linear, normalization, timestep_frequencies, zero_module
 
 
 class TimestepBlock(nn.Module):
@@ -50,7 +55,7 @@ class TimestepEmbedSequential(nn.Sequential, TimestepBlock):
 
 
 class Downsample(nn.Module):
-    """Reference ``model.py:71-97``: conv3x3 stride 2 pad 1 (``use_conv``)."""
+    """Reference ``model.py:71-97``: conv3x3 stride 2 pad 1 (``use_conv``), else avg-pool 2x2 stride 2."""
 
     def __init__(self, channels, use_conv, dims=2, out_channels=None, padding=1):
         super().__init__()
@@ -59,14 +64,22 @@ class Downsample(nn.Module):
         self.use_conv = use_conv
         self.dims = dims
         self.padding = padding
-        if not use_conv:
-            raise NotImplementedError("sd_amd: avg-pool Downsample (conv_resample=False) is not on the SD path")
-        self.op = conv_nd(dims, self.channels, self.out_channels, 3, stride=2, padding=padding)
+        if dims != 2:
+            raise NotImplementedError("sd_amd: dims != 2 is not supported")
+        if use_conv:
+            self.op = conv_nd(dims, self.channels, self.out_channels, 3, stride=2, padding=padding)
+        else:
+            assert self.channels == self.out_channels
+            self.op = avg_pool_nd(dims, kernel_size=2, stride=2)
 
     def _prepare(self, dev):
-        self._pc = ops.PackedConv([(self.op.weight, self.channels)], self.op.bias, device=dev)
+        if self.use_conv:
+            self._pc = ops.PackedConv([(self.op.weight, self.channels)], self.op.bias, device=dev)
 
     def _run(self, x):
+        if not self.use_conv:
+            # the pooled tensor carries no statistics: the consumer's GroupNorm runs its own pass
+            return ops.group_norm_resample(x, None, "down")[1]
         return ops.conv2d(self._pc, x, stride=2, pad=self.padding, gn_stats=True)
 
 
@@ -87,27 +100,33 @@ class Upsample(nn.Module):
         self.use_conv = use_conv
         self.dims = dims
         self.padding = padding
-        if not use_conv:
-            raise NotImplementedError("sd_amd: conv-less Upsample (conv_resample=False) is not on the SD path")
-        self.conv = conv_nd(dims, self.channels, self.out_channels, 3, padding=padding)
+        if dims != 2:
+            raise NotImplementedError("sd_amd: dims != 2 is not supported")
+        if use_conv:
+            self.conv = conv_nd(dims, self.channels, self.out_channels, 3, padding=padding)
 
     def _prepare(self, dev):
-        self._pc = ops.PackedConv([(self.conv.weight, self.channels)], self.conv.bias, device=dev)
+        if self.use_conv:
+            self._pc = ops.PackedConv([(self.conv.weight, self.channels)], self.conv.bias, device=dev)
 
     def _run(self, x):
+        if not self.use_conv:
+            return ops.group_norm_resample(x, None, "up")[1]
         if UPSAMPLE_FOLD or isinstance(x, tuple) or x.shape[-1] % 8:
             return ops.conv2d(self._pc, x, upsample=True, pad=self.padding, gn_stats=True)
         return ops.conv2d(self._pc, ops.upsample_nearest2x_padded(x, self.padding), pad=0, gn_stats=True)
 
 
 class ResBlock(TimestepBlock):
-    """Reference ``model.py:139-252`` (use_scale_shift_norm / up / down are not on the SD path)."""
+    """Reference ``model.py:139-252``.  ``use_scale_shift_norm``: ``emb_layers`` yields (scale, shift) and the
+    ``out_layers`` norm is FiLM-conditioned; ``up`` / ``down``: the block resamples (``h_upd`` on the activated
+    input, ``x_upd`` on the skip; both parameter-free)."""
 
     def __init__(self, channels, emb_channels, dropout, out_channels=None, use_conv=False,
                  use_scale_shift_norm=False, dims=2, use_checkpoint=False, up=False, down=False):
         super().__init__()
-        if use_scale_shift_norm or up or down:
-            raise NotImplementedError("sd_amd: use_scale_shift_norm / resblock_updown are not on the SD path")
+        if dims != 2:
+            raise NotImplementedError("sd_amd: dims != 2 is not supported")
         self.channels = channels
         self.emb_channels = emb_channels
         self.dropout = dropout
@@ -117,9 +136,18 @@ class ResBlock(TimestepBlock):
         self.use_scale_shift_norm = use_scale_shift_norm
         self.in_layers = nn.Sequential(normalization(channels), nn.SiLU(),
                                        conv_nd(dims, channels, self.out_channels, 3, padding=1))
-        self.updown = False
-        self.h_upd = self.x_upd = nn.Identity()
-        self.emb_layers = nn.Sequential(nn.SiLU(), linear(emb_channels, self.out_channels))
+        self.updown = up or down
+        self._resample = "up" if up else "down" if down else None
+        if up:
+            self.h_upd = Upsample(channels, False, dims)
+            self.x_upd = Upsample(channels, False, dims)
+        elif down:
+            self.h_upd = Downsample(channels, False, dims)
+            self.x_upd = Downsample(channels, False, dims)
+        else:
+            self.h_upd = self.x_upd = nn.Identity()
+        self.emb_cols = 2 * self.out_channels if use_scale_shift_norm else self.out_channels
+        self.emb_layers = nn.Sequential(nn.SiLU(), linear(emb_channels, self.emb_cols))
         self.out_layers = nn.Sequential(normalization(self.out_channels), nn.SiLU(), nn.Dropout(p=dropout),
                                         zero_module(conv_nd(dims, self.out_channels, self.out_channels, 3,
                                                             padding=1)))
@@ -154,9 +182,17 @@ class ResBlock(TimestepBlock):
         c1 = x[1].shape[-1] if isinstance(x, tuple) else 0
         # GN+SiLU outputs are written zero-bordered: both 3x3 convs run with pad 0 (mask-free gather)
         gp, cp = ops.gn_conv_pad()
-        xa = self.in_layers[0].norm(x, silu=True, pad=gp)
-        h = ops.conv2d(self._pc1, xa, pad=cp, row_bias=(emb_all, emb_off), gn_stats=True)
-        ha = self.out_layers[0].norm(h, silu=True, pad=gp)
+        if self.updown:
+            # one read of x: resample(SiLU(GN(x))) for conv1 and resample(x) for the skip
+            xa, x = ops.group_norm_resample(x, self.in_layers[0].scale_shift(x), self._resample, silu=True, pad=gp)
+        else:
+            xa = self.in_layers[0].norm(x, silu=True, pad=gp)
+        if self.use_scale_shift_norm:
+            h = ops.conv2d(self._pc1, xa, pad=cp, gn_stats=True)
+            ha = self.out_layers[0].norm_film(h, emb_all, emb_off, silu=True, pad=gp)
+        else:
+            h = ops.conv2d(self._pc1, xa, pad=cp, row_bias=(emb_all, emb_off), gn_stats=True)
+            ha = self.out_layers[0].norm(h, silu=True, pad=gp)
         if self._skip_mode == "identity":
             return ops.conv2d(self._pc2, ha, pad=cp, residual=x, gn_stats=True)
         if self._skip_mode == "fused":
@@ -180,8 +216,10 @@ class UNetModel(nn.Module):
         if context_dim is not None:
             assert use_spatial_transformer, "context_dim needs use_spatial_transformer"
             context_dim = list(context_dim) if isinstance(context_dim, (list, tuple)) else context_dim
-        if num_classes is not None or n_embed is not None:
-            raise NotImplementedError("sd_amd: class-conditional / codebook heads are not on the SD path")
+        if n_embed is not None:
+            raise NotImplementedError("sd_amd: n_embed (the id_predictor codebook head) is not supported")
+        if dims != 2:
+            raise NotImplementedError("sd_amd: dims != 2 is not supported")
         if num_heads_upsample == -1:
             num_heads_upsample = num_heads
         if num_heads == -1:
@@ -227,6 +265,8 @@ class UNetModel(nn.Module):
         time_embed_dim = model_channels * 4
         self.time_embed = nn.Sequential(linear(model_channels, time_embed_dim), nn.SiLU(),
                                         linear(time_embed_dim, time_embed_dim))
+        if self.num_classes is not None:
+            self.label_emb = nn.Embedding(num_classes, time_embed_dim)
         self.input_blocks = nn.ModuleList(
             [TimestepEmbedSequential(conv_nd(dims, in_channels, model_channels, 3, padding=1))])
         input_block_chans = [model_channels]
@@ -241,10 +281,10 @@ class UNetModel(nn.Module):
                 self.input_blocks.append(TimestepEmbedSequential(*layers))
                 input_block_chans.append(ch)
             if level != len(channel_mult) - 1:
-                if resblock_updown:
-                    raise NotImplementedError("sd_amd: resblock_updown is not on the SD path")
                 self.input_blocks.append(TimestepEmbedSequential(
-                    Downsample(ch, conv_resample, dims=dims, out_channels=ch)))
+                    ResBlock(ch, time_embed_dim, dropout, out_channels=ch, dims=dims, use_checkpoint=use_checkpoint,
+                             use_scale_shift_norm=use_scale_shift_norm, down=True)
+                    if resblock_updown else Downsample(ch, conv_resample, dims=dims, out_channels=ch)))
                 input_block_chans.append(ch)
                 ds *= 2
         self.middle_block = TimestepEmbedSequential(
@@ -264,7 +304,10 @@ class UNetModel(nn.Module):
                 if ds in attention_resolutions:
                     layers.append(attn_layer(ch, num_heads_upsample))
                 if level and i == num_res_blocks:
-                    layers.append(Upsample(ch, conv_resample, dims=dims, out_channels=ch))
+                    layers.append(ResBlock(ch, time_embed_dim, dropout, out_channels=ch, dims=dims,
+                                           use_checkpoint=use_checkpoint,
+                                           use_scale_shift_norm=use_scale_shift_norm, up=True)
+                                  if resblock_updown else Upsample(ch, conv_resample, dims=dims, out_channels=ch))
                     ds //= 2
                 self.output_blocks.append(TimestepEmbedSequential(*layers))
         self.out = nn.Sequential(normalization(ch), nn.SiLU(),
@@ -289,7 +332,7 @@ class UNetModel(nn.Module):
         for rb in resblocks:
             rb._prepare(dev)
             rb._emb_off = off
-            off += rb.out_channels
+            off += rb.emb_cols           # 2 * out_channels for a FiLM block: (scale | shift)
             ws.append(rb.emb_layers[1].weight)
             bs.append(rb.emb_layers[1].bias)
         self._emb_total = off
@@ -307,6 +350,9 @@ class UNetModel(nn.Module):
         self.out[0]._prepare(dev)
         self._pc_out = ops.PackedConv([(self.out[2].weight, self.model_channels)], self.out[2].bias, device=dev)
         self._freqs = timestep_frequencies(self.model_channels).to(dev)
+        self._label_table = None
+        if self.num_classes is not None:
+            self._label_table = self.label_emb.weight.detach().to(dev, torch.float32).contiguous()
         self._sts = [m for m in self.modules() if isinstance(m, SpatialTransformer)]
         self._prepared_on = dev
         self._ctx_cache = None
@@ -358,7 +404,17 @@ class UNetModel(nn.Module):
         whose channels follow ``x``'s, i.e. the result of ``forward(torch.cat([x] + concat, 1), ...)``
         (``DiffusionWrapper.forward`` 'concat' / 'hybrid', ``Diffusion/ddpm.py:51-63``) with the concat
         folded into the NCHW → NHWC pack of the input, so the concatenated tensor is never built."""
-        assert (y is not None) == (self.num_classes is not None), "y iff class-conditional"
+        assert (y is not None) == (self.num_classes is not None), \
+            "must specify y if and only if the model is class-conditional"
+        if y is not None:
+            if not torch.is_tensor(y):
+                y = torch.as_tensor(y)
+            assert y.shape == (x.shape[0],), f"y must have shape ({x.shape[0]},), got {tuple(y.shape)}"
+            if not y.is_cuda:
+                # a host tensor is checked here; a device y is not synced (the kernel writes NaN rows instead)
+                if y.numel() and (int(y.min()) < 0 or int(y.max()) >= self.num_classes):
+                    raise IndexError(f"sd_amd.UNetModel: class label out of range [0, {self.num_classes}): "
+                                     f"{y.tolist()}")
         concat = list(concat) if concat is not None else []
         if concat:
             if len(concat) > 3:
@@ -390,6 +446,8 @@ class UNetModel(nn.Module):
         temb = ops.timestep_embedding(t, self._freqs, self.model_channels)
         e1 = ops.linear(self._pc_te0, temb)
         emb = ops.linear(self._pc_te2, e1, silu=True)
+        if y is not None:
+            emb = ops.embedding_add(emb, self._label_table, y.to(device=x.device, dtype=torch.int64))
         emb_all = ops.linear(self._pc_emb, emb, silu=True, out_mode=ops.OUT_ROWS_F32)
         kv, Lc = self._context_kv(context)
         st = {"emb": emb_all, "kv": kv, "Lc": Lc}

@@ -33,6 +33,11 @@ class GroupNorm32(nn.GroupNorm):
         """GroupNorm (+ SiLU) of x materialised (zero-bordered by ``pad``) — one ``sdk_group_norm``."""
         return ops.group_norm(x, self._g, self._b, self.eps, self.num_groups, silu=silu, pad=pad)
 
+    def norm_film(self, x, film, film_off, silu=True, pad=0):
+        """``norm`` with FiLM conditioning, ``GN(x) * (1 + f) + g`` with (f, g) = ``film[:, off : off + 2C]`` — one
+        ``sdk_group_norm_film`` (the ``use_scale_shift_norm`` ResBlock, reference ``model.py:244-248``)."""
+        return ops.group_norm_film(x, self._g, self._b, self.eps, film, film_off, self.num_groups, silu=silu, pad=pad)
+
     def forward(self, x):
         raise NotImplementedError("sd_amd: GroupNorm32 runs fused inside the HIP conv (use the parent block)")
 

@@ -772,6 +772,95 @@ def group_norm(x, gamma, beta, eps, groups=32, silu=True, pad=0, out=None):
     return y
 
 
+def _producer_parts(x):
+    """(part0, nch0, part1, nch1) of the statistics the producing convs attached to x's sources, or
+    (None, 0, None, 0) unless every source carries current ones."""
+    srcs = [t for t in _as_pair(x) if t is not None]
+    parts = [getattr(t, GN_ATTR, None) for t in srcs]
+    parts = [pp if pp is not None and pp[2] == t._version else None for pp, t in zip(parts, srcs)]
+    if not all(pp is not None for pp in parts):
+        return None, 0, None, 0
+    p1, n1 = (parts[1][0], parts[1][1]) if len(parts) > 1 else (None, 0)
+    return parts[0][0], parts[0][1], p1, n1
+
+
+def group_norm_film(x, gamma, beta, eps, film, film_off, groups=32, silu=True, pad=0, out=None):
+    """GroupNorm with FiLM conditioning (+ SiLU): ``silu?(GN(x) * (1 + f) + g)`` with ``f = film[:, off:off+C]``,
+    ``g = film[:, off+C:off+2C]`` (fp32 ``[B, ld]``, the batched ``emb_layers`` GEMM), folded into the
+    per-(batch, channel) affine so x is read once and y written once (``sdk_group_norm_film``)."""
+    args, (B, H, W, Ch), dev = _gn_args(x)
+    _need_cuda(film, "group_norm_film film", torch.float32)
+    if film.dim() != 2 or film.shape[0] != B or film.stride(1) != 1 or film_off < 0 or \
+            film_off + 2 * Ch > film.shape[1]:
+        raise ValueError(f"sd_amd.group_norm_film: film {tuple(film.shape)} has no [{B}, {film_off}:{film_off}+2*{Ch}]")
+    args.groups, args.eps = groups, eps
+    args.gamma, args.beta = gamma.data_ptr(), beta.data_ptr()
+    scale = torch.empty(B, Ch, dtype=torch.float32, device=dev)
+    shift = torch.empty(B, Ch, dtype=torch.float32, device=dev)
+    args.scale, args.shift = scale.data_ptr(), shift.data_ptr()
+    ws = WORKSPACE.get(lib().sdk_group_norm_workspace(B, H * W, Ch), dev)
+    args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    y = _claim(out) if out is not None else torch.empty(B, H + 2 * pad, W + 2 * pad, Ch, dtype=torch.float16,
+                                                          device=dev)
+    p0, n0, p1, n1 = _producer_parts(x)
+    if PROFILER.active:
+        PROFILER.begin("group_norm_film", None)
+    check(lib().sdk_group_norm_film(C.byref(args), _ptr(film), film.stride(0), film_off, 1 if silu else 0, _ptr(y),
+                                    y.shape[-1], H, W, pad, _ptr(p0), n0, _ptr(p1), n1, _stream()),
+          "group_norm_film")
+    if PROFILER.active:
+        PROFILER.end()
+    return y
+
+
+RESAMPLE_MODES = {"down": _lib.RESAMPLE_AVGPOOL2, "up": _lib.RESAMPLE_NEAREST2}
+
+
+def group_norm_resample(x, gn, mode, silu=True, pad=0, act=True, raw=True):
+    """One read of x, two outputs (``sdk_group_norm_resample``): ``(resample(silu?(x*scale + shift)) zero-bordered
+    by pad, resample(x) contiguous)``; ``mode`` 'down' = avg-pool 2x2 stride 2 (odd H / W floor), 'up' = nearest x2.
+    ``gn`` = (scale, shift) fp32 ``[B, C]`` or None (raw only); an output not asked for is None."""
+    args, (B, H, W, Ch), dev = _gn_args(x)
+    if gn is None:
+        act = False
+    else:
+        args.scale, args.shift = gn[0].data_ptr(), gn[1].data_ptr()
+    if not act and not raw:
+        raise ValueError("sd_amd.group_norm_resample: no output asked for")
+    Ho, Wo = (H // 2, W // 2) if mode == "down" else (2 * H, 2 * W)
+    ya = torch.empty(B, Ho + 2 * pad, Wo + 2 * pad, Ch, dtype=torch.float16, device=dev) if act else None
+    yr = torch.empty(B, Ho, Wo, Ch, dtype=torch.float16, device=dev) if raw else None
+    if PROFILER.active:
+        PROFILER.begin("group_norm_resample", None)
+    check(lib().sdk_group_norm_resample(C.byref(args), RESAMPLE_MODES[mode], 1 if silu else 0, H, W, pad, _ptr(ya),
+                                        _ptr(yr), _stream()), "group_norm_resample")
+    if PROFILER.active:
+        PROFILER.end()
+    return ya, yr
+
+
+def embedding_add(emb, table, ids):
+    """``fp16(emb.float() + table[ids])`` — the class-label row added to the timestep embedding
+    (``sdk_embedding_add``).  emb fp16 ``[B, D]``, table fp32 ``[n, D]``, ids int64 ``[B]`` on the device; an id
+    outside ``[0, n)`` gives a NaN row (the table is never read out of range)."""
+    _need_cuda(emb, "embedding_add emb")
+    _need_cuda(table, "embedding_add table", torch.float32)
+    _need_cuda(ids, "embedding_add ids", torch.int64)
+    B, D = emb.shape
+    if table.dim() != 2 or table.shape[1] != D or ids.shape != (B,):
+        raise ValueError(f"sd_amd.embedding_add: emb {tuple(emb.shape)}, table {tuple(table.shape)}, "
+                         f"ids {tuple(ids.shape)}")
+    emb, table, ids = emb.contiguous(), table.contiguous(), ids.contiguous()
+    out = torch.empty(B, D, dtype=torch.float16, device=emb.device)
+    if PROFILER.active:
+        PROFILER.begin("embedding_add", None)
+    check(lib().sdk_embedding_add(_ptr(emb), _ptr(table), _ptr(ids), _ptr(out), B, D, table.shape[0], _stream()),
+          "embedding_add")
+    if PROFILER.active:
+        PROFILER.end()
+    return out
+
+
 def layer_norm(x2d, gamma, beta, eps=1e-5, out=None):
     _need_cuda(x2d, "layer_norm")
     M, Cc = x2d.shape
