@@ -429,14 +429,17 @@ def _conv2d_batch_chunks(pc, x, seg2, gn, row_bias, residual, out, B, kw):
 
 def conv2d(pc: PackedConv, x, *, ksize=None, stride=1, pad=None, pad_end=0, upsample=False, gn=None, silu=False,
            seg2=None, bias=True, row_bias=None, residual=None, out_mode=OUT_NHWC_F16, out=None,
-           variant=None, split_k=None, act=ACT_NONE, gn_stats=False):
+           variant=None, split_k=None, act=ACT_NONE, gn_stats=False, plan_out=None):
     """Run the implicit-GEMM conv.  ``seg2`` = (x2, gn2, silu2) adds a fused 1x1 K segment.
     ``pad_end`` adds zero rows/cols after the source (asymmetric (0,1,0,1) padding).
     ``row_bias`` = (fp32 tensor [B, ld], column offset) — the per-(batch, channel) add.
     ``variant`` / ``split_k`` force a kernel configuration (benchmarks; default: planner
     or autotuner).  ``gn_stats``: the output feeds a GroupNorm — when the chosen plan can, the
     epilogue also emits its per-chunk channel statistics (attached to the returned tensor,
-    consumed by ``group_norm``, which then skips its statistics pass)."""
+    consumed by ``group_norm``, which then skips its statistics pass).  ``plan_out``: a dict that
+    receives the launched plan (``variant``, ``split_k``, ``grid_tiles``, ``gn_chunks`` of the
+    ConvPlanInfo; host integers, so it is safe under graph capture; a conv that runs as batch
+    chunks reports its last chunk)."""
     _claim(out)
     B0 = _as_pair(x)[0].shape[0]
     if B0 > 1 and (_src_bytes(x) >= BUF_LIMIT or (seg2 is not None and _src_bytes(seg2[0]) >= BUF_LIMIT)):
@@ -452,7 +455,8 @@ def conv2d(pc: PackedConv, x, *, ksize=None, stride=1, pad=None, pad_end=0, upsa
             dt = torch.float16 if out_mode in (OUT_NHWC_F16, OUT_GEGLU_F16) else torch.float32
             out = torch.empty(shape, dtype=dt, device=a0.device)
         kw = dict(ksize=ksize, stride=stride, pad=pad, pad_end=pad_end, upsample=upsample, silu=silu, bias=bias,
-                  out_mode=out_mode, variant=variant, split_k=split_k, act=act, gn_stats=gn_stats)
+                  out_mode=out_mode, variant=variant, split_k=split_k, act=act, gn_stats=gn_stats,
+                  plan_out=plan_out)
         return _conv2d_batch_chunks(pc, x, seg2, gn, row_bias, residual, out, B0, kw)
     a = ConvArgs()
     k0 = pc.seg_geom[0][0] if ksize is None else ksize
@@ -516,6 +520,9 @@ def conv2d(pc: PackedConv, x, *, ksize=None, stride=1, pad=None, pad_end=0, upsa
         a.tile_group_m = TILE_GROUP_M
     info = ConvPlanInfo()
     check(lib().sdk_conv2d_plan(C.byref(a), C.byref(info)), "conv2d_plan")
+    if plan_out is not None:
+        plan_out.update(variant=info.variant, split_k=info.split_k, grid_tiles=info.grid_tiles,
+                        gn_chunks=info.gn_chunks)
     if info.workspace_bytes > 0:
         ws = WORKSPACE.get(info.workspace_bytes, dev)
         a.workspace = ws.data_ptr()
@@ -542,10 +549,11 @@ def conv2d(pc: PackedConv, x, *, ksize=None, stride=1, pad=None, pad_end=0, upsa
 
 
 def linear(pc: PackedConv, x2d, *, silu=False, residual=None, out_mode=OUT_NHWC_F16, out=None, bias=True,
-           act=ACT_NONE, n_img=None):
+           act=ACT_NONE, n_img=None, plan_out=None):
     """Token GEMM: x2d [M, K] fp16 → [M, N]; a 1x1 conv over an M x 1 image.  ``silu`` applies to
     the input (prologue), ``act`` to the output (epilogue, before the residual).  ``n_img``: rows per
-    image, for a ``PerImageWeights`` pc (the GEMM runs as M / n_img images of n_img x 1)."""
+    image, for a ``PerImageWeights`` pc (the GEMM runs as M / n_img images of n_img x 1).
+    ``plan_out``: as for ``conv2d``."""
     _claim(out)
     M = x2d.shape[0]
     nb, rows = (1, M) if n_img is None else (M // n_img, n_img)
@@ -557,7 +565,7 @@ def linear(pc: PackedConv, x2d, *, silu=False, residual=None, out_mode=OUT_NHWC_
         x4 = x2d.as_strided((nb, rows, 1, x2d.shape[1]), (rows * x2d.stride(0), x2d.stride(0), x2d.stride(0), 1))
     res4 = residual.view(nb, rows, 1, residual.shape[-1]) if residual is not None else None
     y = conv2d(pc, x4, ksize=1, pad=0, silu=silu, residual=res4, out_mode=out_mode, bias=bias,
-               out=None if out is None else out.view(nb, rows, 1, out.shape[-1]), act=act)
+               out=None if out is None else out.view(nb, rows, 1, out.shape[-1]), act=act, plan_out=plan_out)
     return y.view(M, y.shape[-1])
 
 

@@ -90,7 +90,9 @@ def test_conv_gn_silu_concat_fused_skip_rowbias(ops, conv_variant):
     b1 = torch.randn(Co) * 0.1
     emb = torch.randn(B, 200).float()
     pc1 = ops.PackedConv([(w1, C1 + C2)], b1, device=DEV)
-    y1 = ops.conv2d(pc1, (a.to(DEV), b2.to(DEV)), gn=(sc, sh), silu=True, row_bias=(emb.to(DEV), 17))
+    plan = {}
+    y1 = ops.conv2d(pc1, (a.to(DEV), b2.to(DEV)), gn=(sc, sh), silu=True, row_bias=(emb.to(DEV), 17), plan_out=plan)
+    assert plan["variant"] == 0       # a GN+SiLU prologue: the register-staged kernel, whatever was forced
     ref1 = _conv_ref(xcat, w1.half(), b1, gn=(sc.cpu(), sh.cpu()), silu=True) + emb[:, None, None, 17:17 + Co]
     assert rel_l2(y1, ref1) < 3e-3
     # conv2 with fused 1x1 shortcut over the concat input
@@ -124,7 +126,9 @@ def test_linear_residual_geglu_rows_f32(ops, conv_variant):
     assert yg.shape == (M, inner)
     assert rel_l2(yg, refg) < 3e-3
     # fp32 rows + A-side SiLU (timestep-embedding projections)
-    y32 = ops.linear(pc, x.to(DEV), silu=True, out_mode=ops.OUT_ROWS_F32)
+    plan = {}
+    y32 = ops.linear(pc, x.to(DEV), silu=True, out_mode=ops.OUT_ROWS_F32, plan_out=plan)
+    assert plan["variant"] == 0       # an A-side SiLU: the register-staged kernel, whatever was forced
     ref32 = F.silu(x.float()).half().float() @ w.half().float().T + b
     assert y32.dtype == torch.float32 and rel_l2(y32, ref32) < 2e-3
 
@@ -141,10 +145,13 @@ def test_linear_quick_gelu_act(ops, conv_variant, M, K, N, split):
     h = x.float() @ w.half().float().T + b
     qg = h * torch.sigmoid(1.702 * h)
     x4 = x.to(DEV).view(1, M, 1, K)
+    plan = {}
     y = ops.conv2d(pc, x4, ksize=1, pad=0, act=ops.ACT_QUICK_GELU, residual=r.to(DEV).view(1, M, 1, N),
-                   split_k=split).view(M, N)
+                   split_k=split, plan_out=plan).view(M, N)
+    assert plan["variant"] == 0       # an epilogue act: the register-staged kernel, whatever was forced
     assert rel_l2(y, qg.half().float() + r.float()) < 3e-3
-    y32 = ops.linear(pc, x.to(DEV), act=ops.ACT_QUICK_GELU, out_mode=ops.OUT_ROWS_F32)
+    y32 = ops.linear(pc, x.to(DEV), act=ops.ACT_QUICK_GELU, out_mode=ops.OUT_ROWS_F32, plan_out=plan)
+    assert plan["variant"] == 0
     assert rel_l2(y32, qg) < 2e-3
 
 
