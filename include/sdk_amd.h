@@ -60,7 +60,7 @@ typedef struct {
   int32_t cin;             /* multiple of 8 */
   int32_t ld0, ld1;        /* elements between consecutive pixels of src0 / src1 */
   int32_t h, w;            /* source spatial size (before upsampling) */
-  int32_t ksize;           /* 1 or 3 */
+  int32_t ksize;           /* 1 or 3 (2: sdk_conv_args.upsample_phase only) */
   int32_t stride, pad;
   int32_t upsample;        /* 1: source is read nearest-x2 upsampled (logical 2h x 2w) */
   const float* gn_scale;   /* [batch][cin] or NULL */
@@ -116,6 +116,16 @@ typedef struct {
                               many M-panels, N-tile major inside a group, so the tiles co-resident on one XCD
                               share both their A panels and their W tiles in its L2; 0: the library's choice,
                               1: M-panel major (every N-tile of a panel, then the next panel) */
+  int32_t upsample_phase;  /* 1: the phase form of nearest-x2 + conv3x3 pad 1 (F.interpolate + nn.Conv2d of the
+                              Upsample modules).  Output pixel (2i+a, 2j+b) sees only a 2x2 window of the low-res
+                              image, so the layer is four 2x2 convs, one per parity (a, b), each with K = 4 * cin:
+                              seg[0] = the low-res image with a 1-pixel zero border ([batch][h][w], h = ho/2 + 2,
+                              w = wo/2 + 2), ksize 2, stride 1, pad 0, cin % 64 == 0; weight = the four phase
+                              matrices (phase = 2a + b, weight_batch_stride apart; taps (dy, dx) hold the 3x3
+                              weights that land on window pixel (i+a+dy, j+b+dx)); ho / wo / out = the ordinary x2
+                              NHWC fp16 output.  One segment, no residual / row_bias / act / in-launch split; only
+                              the LDS-DMA tile kernels (a forced variant without the form is not honoured).
+                              gn_partial chunks are phase major inside an image */
 } sdk_conv_args;
 
 #define SDK_TILE_COUNTERS 16384
@@ -502,7 +512,12 @@ int sdk_gelu(const void* x, void* y, int64_t n, sdk_stream_t stream);
 int sdk_upsample_nearest2x_padded(const void* x, int32_t ld_x, void* y, int32_t batch, int32_t h, int32_t w,
                                   int32_t channels, int32_t pad, sdk_stream_t stream);
 
-/* ---------------------------------------------------------------- ADM ("guided diffusion") UNet options
+/* The image itself with a zero border of `pad`: y = [batch][h + 2pad][w + 2pad][channels] fp16 — the source of
+ * the phase-form Upsample conv (sdk_conv_args.upsample_phase, pad 1): a quarter of the x2 image's bytes. */
+int sdk_zero_border(const void* x, int32_t ld_x, void* y, int32_t batch, int32_t h, int32_t w, int32_t channels,
+                    int32_t pad, sdk_stream_t stream);
+
+/* ---------------------------------------------------------------- ADM("guided diffusion") UNet options
  * GroupNorm with FiLM conditioning (+ SiLU), the `use_scale_shift_norm` ResBlock (openai_model/model.py:244-248:
  * out_norm(h) * (1 + scale) + shift, then SiLU): as sdk_group_norm, with film = fp32 [batch][film_ld], the
  * scale at film[b*film_ld + film_off + c] and the shift at film[b*film_ld + film_off + channels + c] (this

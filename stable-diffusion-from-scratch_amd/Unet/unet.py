@@ -43,9 +43,19 @@ class Upsample(nn.Module):
         self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1)
 
     def _prepare(self, dev):
+        from ..openai_model.model import UPSAMPLE_FOLD, UPSAMPLE_MATERIALISE
         self._pc = ops.PackedConv([(self.conv.weight, self.in_channels)], self.conv.bias, device=dev)
+        self._ppc = None
+        if self.in_channels % 64 == 0 and not (UPSAMPLE_FOLD or UPSAMPLE_MATERIALISE):
+            self._ppc = ops.PhaseConv(self.conv.weight, self.in_channels, self.conv.bias, device=dev)
 
     def _run(self, x):
+        # Default: the phase form (openai_model/model.py) — four 2x2 convs over the zero-bordered low-res image;
+        # neither the x2 image nor its temporary exists.  The routes below are the A/B switches and the fallback
+        # for channel counts that are no multiple of 64.
+        from ..openai_model.model import upsample_phase_ok
+        if getattr(self, "_ppc", None) is not None and upsample_phase_ok(x):
+            return ops.conv2d(self._ppc, ops.zero_border(x, 1), phase=True, gn_stats=True)
         # the output feeds the next ResnetBlock's norm1: the conv emits its GroupNorm statistics.  As in the UNet's
         # Upsample (openai_model/model.py), the nearest-x2 image is written zero-bordered and the 3x3 conv runs
         # unmasked with pad 0 on the linear A issue, instead of folding the upsample into every DMA address

@@ -30,7 +30,7 @@ class ConvArgs(C.Structure):
                 ("residual", vp), ("res_ld", i32), ("out", vp), ("out_ld", i32), ("out_mode", i32),
                 ("split_k", i32), ("workspace", vp), ("workspace_bytes", i64), ("variant_hint", i32),
                 ("act", i32), ("gn_partial", vp), ("weight_batch_stride", i64), ("split_inlaunch", i32),
-                ("tile_counters", vp), ("tile_group_m", i32)]
+                ("tile_counters", vp), ("tile_group_m", i32), ("upsample_phase", i32)]
 
 
 class ConvPlanInfo(C.Structure):
@@ -102,7 +102,7 @@ EXPORTS = ["sdk_conv2d_plan", "sdk_conv2d", "sdk_group_norm_workspace", "sdk_gro
            "sdk_attention", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_posterior_step", "sdk_masked_q_sample", "sdk_concat_nchw_to_nhwc", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
            "sdk_diag_gaussian_sample", "sdk_stochastic_encode", "sdk_token_embedding", "sdk_extract_patches",
            "sdk_fold_patches", "sdk_vq_code_norms", "sdk_vq_nearest_splits", "sdk_vq_nearest", "sdk_vq_lookup", "sdk_vq_remap",
-           "sdk_upsample_bilinear2x", "sdk_upsample_nearest2x_padded", "sdk_gelu",
+           "sdk_upsample_bilinear2x", "sdk_upsample_nearest2x_padded", "sdk_zero_border", "sdk_gelu",
            "sdk_group_norm_film", "sdk_group_norm_resample", "sdk_embedding_add", "sdk_last_error", "sdk_version", "sdk_kernel_name",
            "sdk_probe_mfma_flops", "sdk_probe_mfma", "sdk_probe_copy", "sdk_probe_copy_ex"]
 
@@ -136,6 +136,7 @@ def lib():
     L.sdk_embedding_add.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     L.sdk_upsample_bilinear2x.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     L.sdk_upsample_nearest2x_padded.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, vp]
+    L.sdk_zero_border.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, vp]
     L.sdk_gelu.argtypes = [vp, vp, i64, vp]
     L.sdk_layer_norm.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, f32, vp]
     L.sdk_attention.argtypes = [C.POINTER(AttentionArgs), vp]

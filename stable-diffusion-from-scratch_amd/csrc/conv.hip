@@ -83,7 +83,30 @@ struct Params {
   unsigned long long* stamps;   // diagnostics build only: 8 shader-clock stamps per workgroup, or null
   int stamps_rt;                // diagnostics: slots 6 / 7 = s_memrealtime at entry / end (SDK_CONV_STAMPS=2)
   int simple;           // token GEMM (one segment, 1x1 stride 1, no masks, one source): linear A / W K offsets
+  // phase form of nearest-x2 + 3x3 (sdk_conv_args.upsample_phase): four 2x2 convs over the zero-bordered low-res
+  // image, one per output parity (a, b).  GEMM rows are phase major, each phase's ph_rows = batch * hw_out rows
+  // padded to ph_rows_pad (a multiple of the M-tile, so no tile straddles two phases' weights): row
+  // m = phase * ph_rows_pad + (img * ho + i) * wo + j gathers the 2x2 window at (i + a, j + b) and stores to
+  // output pixel (img, 2i + a, 2j + b); ho / wo / hw_out are the LOW-RES extents, M = 4 * ph_rows_pad
+  int phase, ph_rows, ph_rows_pad;
 };
+
+// Phase form: output row (pixel index of the 2ho x 2wo NHWC output) of GEMM row m, or -1 for a padding row
+__device__ __forceinline__ int phase_out_row(const Params& p, int m) {
+  const int ph = m / p.ph_rows_pad, rp = m - ph * p.ph_rows_pad;
+  if (ph > 3 || rp >= p.ph_rows) return -1;
+  const int img = rp / p.hw_out, rem = rp - img * p.hw_out;
+  const int i = rem / p.wo, j = rem - i * p.wo;
+  return (img * 2 * p.ho + 2 * i + (ph >> 1)) * (2 * p.wo) + 2 * j + (ph & 1);
+}
+
+// the output row an epilogue stores GEMM row m to (-1: none).  PH: compiled with the phase form (only the
+// linear-issue conv_glds_kernel and the split-K reduces; everything else keeps its code)
+template <bool PH>
+__device__ __forceinline__ int out_row(const Params& p, int m) {
+  if (PH && p.phase) return phase_out_row(p, m);
+  return m < p.M ? m : -1;
+}
 
 // diagnostics build: s_memtime at kernel entry / after the prologue / after the K loop / at the end (+ after
 // epilogue groups 0-3 at 4-7), by
@@ -623,7 +646,7 @@ __device__ __forceinline__ void gn_block_stats(const half_t* blk, float2* dst) {
 // after every wave parked its blocks: one thread per tile channel merges the WM waves x NBLK row
 // blocks (BR rows each) of its column and stores the tile's pair; `wave_stats(w)` = wave w's
 // parked array [NBLK][TN]
-template <int WM, int WN, int TN, int NBLK, int BR, int TBM, int TBN, class F>
+template <int WM, int WN, int TN, int NBLK, int BR, int TBM, int TBN, bool PH = false, class F>
 __device__ __forceinline__ void gn_tile_store(const Params& p, int m0, int n0, F wave_stats) {
   const int t = threadIdx.x;
   if (t >= TBN || n0 + t >= p.N) return;
@@ -640,7 +663,12 @@ __device__ __forceinline__ void gn_tile_store(const Params& p, int m0, int n0, F
       r.y += b.y + dl * dl * n * f;
       n += (float)BR;
     }
-  const int b0 = m0 / p.hw_out, chunk = (m0 - b0 * p.hw_out) / TBM;
+  int b0 = m0 / p.hw_out, chunk = (m0 - b0 * p.hw_out) / TBM;
+  if (PH && p.phase) {   // an image's chunks: phase major, then the phase's M-tiles inside the image (equal counts)
+    const int ph = m0 / p.ph_rows_pad, rp = m0 - ph * p.ph_rows_pad;
+    b0 = rp / p.hw_out;
+    chunk = ph * (p.hw_out / TBM) + (rp - b0 * p.hw_out) / TBM;
+  }
   p.gnp[((size_t)b0 * p.gn_nch + chunk) * p.N + n0 + t] = r;
 }
 
@@ -668,7 +696,7 @@ __device__ __forceinline__ void gn_acc_add(GnAcc& a, const h8& v, bool first) {
 // workgroup (stage_epi_vectors, before the K loop): the epilogue reads them with ds_read instead of
 // waiting on a global load per 32-row block.  ``bias_s`` / ``rb_s`` = nullptr fall back to global.
 // Residual rows are loaded one block ahead (issued before the current block's LDS round trip).
-template <int FM, int FN, bool GN = false>
+template <int FM, int FN, bool GN = false, bool PH = false>
 __device__ __forceinline__ void epilogue_lds(const Params& p, f16v (&acc)[FM][FN], int m0, int n0, int m_w, int n_w,
                                              half_t* wbuf, const float* bias_s = nullptr,
                                              const float* rb_s = nullptr) {
@@ -819,7 +847,8 @@ __device__ __forceinline__ void epilogue_lds(const Params& p, f16v (&acc)[FM][FN
           for (int qq = 0; qq < 8; ++qq) v[qq] = (half_t)((float)v[qq] + (float)rcur[r][qq]);
         }
         if constexpr (GN) *reinterpret_cast<h8*>(wbuf + row * EPI_RS + c8 * 8) = v;   // final values for the stats
-        if (m < p.M && n < p.N) st_out16(out + (size_t)m * p.out_ld + n, v);
+        const int mo = out_row<PH>(p, m);
+        if (mo >= 0 && n < p.N) st_out16(out + (size_t)mo * p.out_ld + n, v);
       }
       if constexpr (GN) {   // full tiles only: every row stored
         if (nt == 2) gn_block_stats<32, 64, EPI_RS>(wbuf, gst + i * TN + jp * 32);
@@ -859,7 +888,7 @@ __device__ __forceinline__ void epi16_load_res(const Params& p, int mt, int nb, 
   }
 }
 
-template <int NB, bool GN = false>
+template <int NB, bool GN = false, bool PH = false>
 __device__ __forceinline__ void epi16_group(const Params& p, const f4* a, int mt, int nb, int n0, int bw, bool rb_vec,
                                             half_t* wbuf, const float* bias_s, const float* rb_s, const h8 (&rr)[2],
                                             float2* gdst = nullptr) {
@@ -957,14 +986,15 @@ __device__ __forceinline__ void epi16_group(const Params& p, const f4* a, int mt
       for (int q = 0; q < 8; ++q) v[q] = (half_t)((float)v[q] + (float)rr[r][q]);
     }
     if constexpr (GN) *reinterpret_cast<h8*>(wbuf + row * EPG_RS + c8 * 8) = v;   // final values for the stats
-    if (m < p.M && n < p.N) st_out16(out + (size_t)m * p.out_ld + n, v);
+    const int mo = out_row<PH>(p, m);
+    if (mo >= 0 && n < p.N) st_out16(out + (size_t)mo * p.out_ld + n, v);
   }
   if constexpr (GN) gn_block_stats<16, 16 * NB, EPG_RS>(wbuf, gdst);   // full tiles only: every row stored
 }
 
 // groups (i, g) flattened; the residual rows of group q+1 are loaded while group q is written
 // (GN: per-channel statistics of the stored values, parked at wbuf + EPG_BYTES — gn_tile_store)
-template <int FM, int FN, bool GN = false>
+template <int FM, int FN, bool GN = false, bool PH = false>
 __device__ __forceinline__ void epilogue16_tile(const Params& p, f4 (&acc)[FM][FN], int m0, int n0, int m_w, int n_w,
                                                 half_t* wbuf, const float* bias_s = nullptr,
                                                 const float* rb_s = nullptr) {
@@ -991,10 +1021,10 @@ __device__ __forceinline__ void epilogue16_tile(const Params& p, f4 (&acc)[FM][F
     if (mt < p.M) {
       const int bw = min(mt + px, p.M - 1) / p.hw_out;
       if (g < FN / 4)
-        epi16_group<4, GN>(p, &acc[i][4 * g], mt, n0 + n_w + 64 * g, n0, bw, rb_vec, wbuf, bias_s, rb_s, rcur,
+        epi16_group<4, GN, PH>(p, &acc[i][4 * g], mt, n0 + n_w + 64 * g, n0, bw, rb_vec, wbuf, bias_s, rb_s, rcur,
                            gst + i * TN + 64 * g);
       else
-        epi16_group<2, GN>(p, &acc[i][FN - 2], mt, n0 + n_w + 16 * (FN - 2), n0, bw, rb_vec, wbuf, bias_s, rb_s,
+        epi16_group<2, GN, PH>(p, &acc[i][FN - 2], mt, n0 + n_w + 16 * (FN - 2), n0, bw, rb_vec, wbuf, bias_s, rb_s,
                            rcur, gst + i * TN + 64 * g);
     }
     if (q < 4) ph_stamp(p, 4 + q);
@@ -1122,6 +1152,7 @@ struct DmaSrc {
   __amdgpu_buffer_rsrc_t a0, a1, s0, s1, w;
 };
 
+template <bool PH = false>
 __device__ __forceinline__ DmaSrc make_dma_src(const Params& p, int m0) {
   const Seg& g0 = p.seg[0];
   const Seg& g1 = p.seg[1];
@@ -1133,14 +1164,29 @@ __device__ __forceinline__ DmaSrc make_dma_src(const Params& p, int m0) {
   d.s0 = ph_rsrc(two ? g1.src0 : g0.src0, two ? (long long)p.M * g1.ld0 * 2 : 0);
   d.s1 = ph_rsrc(two && g1.src1 ? g1.src1 : g0.src0, two && g1.src1 ? (long long)p.M * g1.ld1 * 2 : 0);
   // per-image weights: an M-tile lies inside one image (planner), so one base per workgroup
-  d.w = ph_rsrc(p.wbs ? p.W + (size_t)(m0 / p.hw_out) * p.wbs : p.W, (long long)p.wrows * p.ldw * 2);
+  // (phase form: one base per phase — the planner pads every phase to whole M-tiles)
+  const int wi = (PH && p.phase) ? m0 / p.ph_rows_pad : m0 / p.hw_out;
+  d.w = ph_rsrc(p.wbs ? p.W + (size_t)wi * p.wbs : p.W, (long long)p.wrows * p.ldw * 2);
   return d;
 }
 
 // Per-lane context of A row m (output pixel) for segment 0: pixb = source pixel index of
 // the tap window origin, msk = bit per in-image tap; upsample: pixb = b*h, msk = oy<<16|ox.
-__device__ __forceinline__ void a_row_ctx(const Params& p, int m, unsigned& pixb, unsigned& msk) {
+// Phase form: pixb = the 2x2 window origin (i + a, j + b) of the row's phase in the zero-bordered low-res image
+// (every tap in range).  Returns whether m is a row of the problem (not past M, not a phase's padding row).
+template <bool PH = false>
+__device__ __forceinline__ bool a_row_ctx(const Params& p, int m, unsigned& pixb, unsigned& msk) {
   const Seg& g0 = p.seg[0];
+  if (PH && p.phase) {
+    const int ph = m / p.ph_rows_pad, rp = m - ph * p.ph_rows_pad;
+    const bool valid = m < p.M && rp < p.ph_rows;
+    const int rr = valid ? rp : 0;
+    const int b = rr / p.hw_out, rem = rr - b * p.hw_out;
+    const int oy = rem / p.wo, ox = rem - oy * p.wo;
+    pixb = (unsigned)((b * g0.h + oy + (ph >> 1)) * g0.w + ox + (ph & 1));
+    msk = valid ? 0xfu : 0u;
+    return valid;
+  }
   const bool valid = m < p.M;
   const int mm = valid ? m : 0;
   const int b = mm / p.hw_out, rem = mm - b * p.hw_out;
@@ -1161,6 +1207,7 @@ __device__ __forceinline__ void a_row_ctx(const Params& p, int m, unsigned& pixb
   }
   pixb = pb;
   msk = mk;
+  return valid;
 }
 
 __device__ __forceinline__ unsigned w_row_ctx(const Params& p, int n, int rch) {
@@ -1310,7 +1357,8 @@ __global__ void __launch_bounds__(CF::NT, CF::OCC * CF::NW / 4) conv_glds_kernel
   const int m0 = tm * CF::TBM, n0 = tn * CF::TBN;
   const int kt0 = sidx * p.kt_per_split, kt1 = min(p.kt_total, kt0 + p.kt_per_split);
   const int lrow = lane >> 3;
-  const DmaSrc d = make_dma_src(p, m0);
+  constexpr bool PH = SIMPLE == 1;   // the phase form runs on this instantiation only (build_params)
+  const DmaSrc d = make_dma_src<PH>(p, m0);
   // per piece j (rows (j*NW + wave)*8 + lrow of the stage): A -> (pixb, msk), W -> byte offset
   unsigned cx[GPW], cy[GPW], cz[SIMPLE == 2 ? GPW : 1];
 #pragma unroll
@@ -1322,8 +1370,8 @@ __global__ void __launch_bounds__(CF::NT, CF::OCC * CF::NW / 4) conv_glds_kernel
       if (piece * 8 < CF::TBM) {
         if constexpr (SIMPLE != 0) {   // the tap window origin's row, 16-B chunk rch of the K step
           const int m = m0 + piece * 8 + lrow;
-          a_row_ctx(p, m, x, y);
-          x = m < p.M ? __umul24(x, (unsigned)p.seg[0].ld0 * 2u) + (unsigned)rch * 16u : PH_OOB;
+          const bool live = a_row_ctx<PH>(p, m, x, y);
+          x = live ? __umul24(x, (unsigned)p.seg[0].ld0 * 2u) + (unsigned)rch * 16u : PH_OOB;
           if constexpr (SIMPLE == 2) {   // the shortcut segment: output pixel m of each concat source
             y = m < p.M ? __umul24((unsigned)m, (unsigned)p.seg[1].ld0 * 2u) + (unsigned)rch * 16u : PH_OOB;
             cz[j] = m < p.M ? __umul24((unsigned)m, (unsigned)p.seg[1].ld1 * 2u) + (unsigned)rch * 16u : PH_OOB;
@@ -1723,16 +1771,16 @@ __global__ void __launch_bounds__(CF::NT, CF::OCC * CF::NW / 4) conv_glds_kernel
   auto gn_store = [&](int scratch_halfs, auto blk_rows) __attribute__((always_inline)) {
     constexpr int BR = decltype(blk_rows)::value;
     __syncthreads();
-    gn_tile_store<CF::WM, CF::WN, CF::TN, CF::TM / BR, BR, CF::TBM, CF::TBN>(
+    gn_tile_store<CF::WM, CF::WN, CF::TN, CF::TM / BR, BR, CF::TBM, CF::TBN, PH>(
         p, m0, n0, [&](int w) { return reinterpret_cast<const float2*>(lds + w * WSCR + scratch_halfs); });
   };
   if constexpr (CF::M16) {
     static_assert(CF::FN16 % 4 == 0 || CF::FN16 % 4 == 2, "epilogue16_tile groups: 64- and 32-channel groups");
     if (lds_epi && p.gnp) {
-      epilogue16_tile<CF::FM16, CF::FN16, true>(p, acc16, m0, n0, wm * CF::TM, wn * CF::TN, wscr, bias_s, rb_s);
+      epilogue16_tile<CF::FM16, CF::FN16, true, PH>(p, acc16, m0, n0, wm * CF::TM, wn * CF::TN, wscr, bias_s, rb_s);
       gn_store(EPG_BYTES / 2, std::integral_constant<int, 16>{});
     } else if (lds_epi) {
-      epilogue16_tile<CF::FM16, CF::FN16>(p, acc16, m0, n0, wm * CF::TM, wn * CF::TN, wscr, bias_s, rb_s);
+      epilogue16_tile<CF::FM16, CF::FN16, false, PH>(p, acc16, m0, n0, wm * CF::TM, wn * CF::TN, wscr, bias_s, rb_s);
     } else {
       epilogue16_tile_direct<CF::FM16, CF::FN16>(p, acc16, m0, n0, wm * CF::TM, wn * CF::TN, sidx);
     }
@@ -1740,10 +1788,10 @@ __global__ void __launch_bounds__(CF::NT, CF::OCC * CF::NW / 4) conv_glds_kernel
     return;
   }
   if (lds_epi && p.gnp) {
-    epilogue_lds<CF::FM, CF::FN, true>(p, acc, m0, n0, wm * CF::TM, wn * CF::TN, wscr, bias_s, rb_s);
+    epilogue_lds<CF::FM, CF::FN, true, PH>(p, acc, m0, n0, wm * CF::TM, wn * CF::TN, wscr, bias_s, rb_s);
     gn_store(EPI_BYTES / 2, std::integral_constant<int, 32>{});
   } else if (lds_epi) {
-    epilogue_lds<CF::FM, CF::FN>(p, acc, m0, n0, wm * CF::TM, wn * CF::TN, wscr, bias_s, rb_s);
+    epilogue_lds<CF::FM, CF::FN, false, PH>(p, acc, m0, n0, wm * CF::TM, wn * CF::TN, wscr, bias_s, rb_s);
   } else {
     epilogue_direct<CF::FM, CF::FN>(p, acc, m0, n0, wm * CF::TM, wn * CF::TN, sidx);
   }
@@ -2325,6 +2373,8 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(Params p) {
   const size_t total = (size_t)p.M * groups;
   for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
     const int m = (int)(e / groups), n = (int)(e - (size_t)m * groups) * 8;
+    const int mo = out_row<true>(p, m);   // phase form (fp16 NHWC only): the slab row's output pixel; padding rows skipped
+    if (mo < 0) continue;
     float vv[1][8];
     slab_sum8<1>(p, {m}, n, vv);
     float (&v)[8] = vv[0];
@@ -2342,7 +2392,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(Params p) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = (half_t)((float)o[j] + (float)rr[j]);
       }
-      *reinterpret_cast<h8*>(reinterpret_cast<half_t*>(p.out) + (size_t)m * p.out_ld + n) = o;
+      *reinterpret_cast<h8*>(reinterpret_cast<half_t*>(p.out) + (size_t)mo * p.out_ld + n) = o;
     } else {
       float* out = reinterpret_cast<float*>(p.out);
 #pragma unroll
@@ -2366,7 +2416,19 @@ __global__ void __launch_bounds__(256) splitk_reduce_gn_kernel(Params p) {
   __shared__ float2 red[32][64];
   const int tc = threadIdx.x & 7, tr = threadIdx.x >> 3;
   const int b = blockIdx.x / p.gn_nch, chunk = blockIdx.x - b * p.gn_nch;
-  const int R = p.hw_out / p.gn_nch;
+  // phase form: an image's rows in chunk order are phase major (4 * hw_out of them); row ri of the image is
+  // slab row ph * ph_rows_pad + b * hw_out + rem and output pixel (b, 2i + a, 2j + b)
+  const int R = (p.phase ? 4 : 1) * p.hw_out / p.gn_nch;
+  auto row_of = [&](int ri, int& mv, int& mo) __attribute__((always_inline)) {
+    if (!p.phase) {
+      mv = mo = b * p.hw_out + ri;
+      return;
+    }
+    const int ph = ri / p.hw_out, rem = ri - ph * p.hw_out;
+    const int i = rem / p.wo, j = rem - i * p.wo;
+    mv = ph * p.ph_rows_pad + b * p.hw_out + rem;
+    mo = (b * 2 * p.ho + 2 * i + (ph >> 1)) * (2 * p.wo) + 2 * j + (ph & 1);
+  };
   const int n = blockIdx.y * 64 + tc * 8;
   const bool colok = n < p.N;
   GnAcc ga;
@@ -2374,8 +2436,9 @@ __global__ void __launch_bounds__(256) splitk_reduce_gn_kernel(Params p) {
   if (colok) epi_add8(p, b, n, bi, rbv);   // the thread's columns and image are fixed
   for (int r = tr; r < R && colok; r += 64) {   // rows r and r + 32 together
     const bool two = r + 32 < R;
-    const int m0 = b * p.hw_out + chunk * R + r;
-    const int mm[2] = {m0, two ? m0 + 32 : m0};
+    int mm[2], mo[2];
+    row_of(chunk * R + r, mm[0], mo[0]);
+    row_of(chunk * R + (two ? r + 32 : r), mm[1], mo[1]);
     h8 rr[2] = {h8{}, h8{}};
     if (p.res) {
 #pragma unroll
@@ -2393,7 +2456,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_gn_kernel(Params p) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = (half_t)((float)o[j] + (float)rr[q][j]);
       }
-      *reinterpret_cast<h8*>(reinterpret_cast<half_t*>(p.out) + (size_t)mm[q] * p.out_ld + n) = o;
+      *reinterpret_cast<h8*>(reinterpret_cast<half_t*>(p.out) + (size_t)mo[q] * p.out_ld + n) = o;
       gn_acc_add(ga, o, r == tr && q == 0);
     }
   }
@@ -2770,6 +2833,21 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
   p.M = a->batch * p.hw_out;
   p.N = a->cout;
   p.nseg = a->nseg;
+  // phase form of nearest-x2 + 3x3 (Params::phase): the kernels see the low-res grid, four times
+  const bool phase = a->upsample_phase != 0;
+  if (phase) {
+    if (a->nseg != 1 || a->out_mode != SDK_OUT_NHWC_F16 || a->residual || a->row_bias || a->act != SDK_ACT_NONE ||
+        a->split_inlaunch || (a->ho & 1) || (a->wo & 1))
+      return fail(SDK_EINVAL, "conv2d: the phase form is one segment, fp16 NHWC, even output extents, no residual / "
+                              "row_bias / act / in-launch split");
+    if (a->weight_batch_stride <= 0)
+      return fail(SDK_EINVAL, "conv2d: the phase form needs the four phase matrices (weight_batch_stride)");
+    if ((double)a->batch * p.hw_out >= 2147483647.0 / 8) return fail(SDK_EINVAL, "conv2d: phase form: too many rows");
+    p.phase = 1;
+    p.ho = a->ho / 2; p.wo = a->wo / 2; p.hw_out = p.ho * p.wo;
+    p.ph_rows = p.ph_rows_pad = a->batch * p.hw_out;
+    p.M = 4 * p.ph_rows;   // the planner pads it per phase once the M-tile is known
+  }
   double kreal = 0;
   int kt = 0, koff = 0;
   for (int s = 0; s < a->nseg; ++s) {
@@ -2780,14 +2858,23 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
       return fail(SDK_EINVAL, "conv2d: cin/c_split must be positive multiples of 8 (c_split <= cin)");
     if (g.c_split < g.cin && !g.src1) return fail(SDK_EINVAL, "conv2d: concat without src1");
     if (g.ld0 % 8 || (g.c_split < g.cin && g.ld1 % 8)) return fail(SDK_EINVAL, "conv2d: ld must be a multiple of 8");
-    if (g.ksize != 1 && g.ksize != 3) return fail(SDK_EINVAL, "conv2d: ksize must be 1 or 3");
+    if (g.ksize != 1 && g.ksize != 3 && !(phase && g.ksize == 2))
+      return fail(SDK_EINVAL, "conv2d: ksize must be 1 or 3 (2: the phase form)");
     if ((g.gn_scale == nullptr) != (g.gn_shift == nullptr)) return fail(SDK_EINVAL, "conv2d: gn scale/shift pair");
     const int lh = g.upsample ? 2 * g.h : g.h, lw = g.upsample ? 2 * g.w : g.w;
     if (g.pad_end < 0 || g.pad_end > 2 || (g.pad_end && g.upsample))
       return fail(SDK_EINVAL, "conv2d: pad_end must be 0..2 (no upsample)");
     // zero padding is implicit (taps outside the source read zeros), so pad_end only widens the grid
-    const int eh = (lh + 2 * g.pad + g.pad_end - g.ksize) / g.stride + 1;
-    const int ew = (lw + 2 * g.pad + g.pad_end - g.ksize) / g.stride + 1;
+    int eh = (lh + 2 * g.pad + g.pad_end - g.ksize) / g.stride + 1;
+    int ew = (lw + 2 * g.pad + g.pad_end - g.ksize) / g.stride + 1;
+    if (phase) {   // the source is the low-res image with its 1-pixel zero border; the output is the x2 image
+      if (g.ksize != 2 || g.stride != 1 || g.pad || g.pad_end || g.upsample || g.h < 3 || g.w < 3 || g.cin % BK ||
+          g.c_split != g.cin || g.gn_scale || g.silu)
+        return fail(SDK_EINVAL, "conv2d: the phase form reads one zero-bordered source with 2x2 taps, stride 1, "
+                                "pad 0, cin % 64 == 0, no transform");
+      eh = 2 * (g.h - 2);
+      ew = 2 * (g.w - 2);
+    }
     if (eh != a->ho || ew != a->wo) return fail(SDK_EINVAL, "conv2d: output size does not match source geometry");
     d.src0 = (const half_t*)g.src0; d.src1 = (const half_t*)g.src1;
     d.gscale = g.gn_scale; d.gshift = g.gn_shift;
@@ -2864,12 +2951,19 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
     return best;
   };
   if (p.wbs && transform) return fail(SDK_EINVAL, "conv2d: per-image weights need a transform-free operand");
+  if (phase && p.simple != 1) return fail(SDK_EINVAL, "conv2d: the phase form runs on the linear A issue only");
+  // the phase form's row map lives in conv_glds_kernel (its fp16 epilogues) and the split-K reduces
+  auto phase_capable = [](int v) {
+    return (v >= 2 && v <= 7 && v != 5) || (v >= 16 && v <= 19) || (v >= 22 && v <= 26) || (v >= 31 && v <= 33) ||
+           v == 38 || v == 40;
+  };
   if (!transform) {
     double best = -1;
     for (const Opt& o : opts) {
       if (a->out_mode == SDK_OUT_GEGLU_F16 && !o.geglu_ok) continue;
-      if (p.wbs && p.hw_out % o.bm) continue;   // per-image weights: M-tiles inside one image
-      const int tmm = (p.M + o.bm - 1) / o.bm, tnn = (p.N + o.bn - 1) / o.bn;
+      if (phase ? !phase_capable(o.variant) : (p.wbs && p.hw_out % o.bm)) continue;   // per-image weights: M-tiles inside one image
+      const int tmm = phase ? 4 * ((p.ph_rows + o.bm - 1) / o.bm) : (p.M + o.bm - 1) / o.bm;
+      const int tnn = (p.N + o.bn - 1) / o.bn;
       const double eff = (double)p.M * p.N / ((double)tmm * o.bm * tnn * o.bn);
       double fill;
       const bool can_split = a->out_mode != SDK_OUT_GEGLU_F16 && a->cout % 8 == 0;
@@ -2971,15 +3065,20 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
     static const int fbn[41] = {128, 0, 256, 128, 128, 320, 160, 320, 256, 256, 256, 256, 256, 256, 256, 256, 128,
                                 128, 128, 256, 256, 256, 320, 320, 160, 256, 128, 256, 256, 256, 256, 160, 128, 160,
                                 0, 0, 0, 0, 320, 320, 256};
-    if (!p.wbs || (forced != 0 && p.hw_out % fbm[fbase] == 0)) {
+    if (phase ? phase_capable(forced) : (!p.wbs || (forced != 0 && p.hw_out % fbm[fbase] == 0))) {
       var = forced;
       tbm = fbm[fbase];
       tbn = fbn[fbase];
       best_split = 0;
     }
   }
-  if (p.wbs && (var == 0 || p.hw_out % tbm))
+  if (phase) {
+    if (!phase_capable(var)) return fail(SDK_EINVAL, "conv2d: the phase form found no LDS-DMA tile plan");
+    p.ph_rows_pad = (p.ph_rows + tbm - 1) / tbm * tbm;   // no M-tile straddles two phases
+    p.M = 4 * p.ph_rows_pad;
+  } else if (p.wbs && (var == 0 || p.hw_out % tbm)) {
     return fail(SDK_EINVAL, "conv2d: per-image weights: no LDS-DMA tile fits inside one image");
+  }
   p.variant = var;
   p.tiles_m = (p.M + tbm - 1) / tbm;
   p.tiles_n = (p.N + tbn - 1) / tbn;
@@ -3027,7 +3126,8 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
     info->grid_tiles = tiles;
     info->workspace_bytes = ws;
     info->variant = var;
-    info->flops = 2.0 * p.M * (double)p.N * kreal;
+    // the executed FLOPs: the phase form's K is 4 * cin over the same output pixels (padding rows not counted)
+    info->flops = 2.0 * (phase ? 4.0 * p.ph_rows : (double)p.M) * (double)p.N * kreal;
   }
   if (split > 1) {
     if (a->cout % 8) return fail(SDK_EINVAL, "conv2d: split-K needs cout % 8 == 0 (pass split_k = 1)");
@@ -3040,8 +3140,9 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
                     (var >= 31 && var <= 33) || var == 38 || var == 40;   // 8 / 9: the phased kernel's 32x32x16 epilogue
   int gn_nch = 0;
   if (a->out_mode == SDK_OUT_NHWC_F16) {
-    if (split > 1 && !p.inl) gn_nch = p.hw_out % 64 == 0 ? p.hw_out / 64 : 1;
-    else if (glds && p.hw_out % tbm == 0) gn_nch = p.hw_out / tbm;   // in-launch split: the combining tile emits
+    const int hw_img = (phase ? 4 : 1) * p.hw_out;   // output pixels of one image
+    if (split > 1 && !p.inl) gn_nch = hw_img % 64 == 0 ? hw_img / 64 : 1;
+    else if (glds && p.hw_out % tbm == 0) gn_nch = hw_img / tbm;   // in-launch split: the combining tile emits
   }
   if (info) info->gn_chunks = gn_nch;
   if (a->gn_partial) {

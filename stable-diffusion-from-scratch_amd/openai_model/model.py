@@ -12,7 +12,8 @@ every conv/linear/norm/attention runs in libsdk_amd.so:
   ``checkpoint(..., flag=False)`` evaluates it twice, ``openai_model/utils.py:217-221``).
 * The skip concat ``torch.cat([h, hs.pop()], 1)`` is never materialised: the
   next block reads both tensors as one K range.
-* Upsample's nearest-x2 is folded into its conv's address generation.
+* Upsample's nearest-x2 + conv3x3 runs as four 2x2 convs over the low-res image, one per output parity
+  (``ops.PhaseConv``): the x2 image is never written.
 * All 22 ResBlock ``emb_layers`` projections run as ONE GEMM per step.
 * The ADM options: ``use_scale_shift_norm`` folds the FiLM (scale, shift) into the GroupNorm affine
   (``ops.group_norm_film``: no extra pass over the activation); a resampling ResBlock (``resblock_updown``)
@@ -83,15 +84,24 @@ class Downsample(nn.Module):
         return ops.conv2d(self._pc, x, stride=2, pad=self.padding, gn_stats=True)
 
 
-# the UNet Upsample materialises the nearest-x2 image zero-bordered and runs its 3x3 conv unmasked (the linear A
-# issue of the LDS-DMA kernels) instead of folding the upsample into every DMA address; SD_AMD_UPSAMPLE_FOLD=1
-# restores the folded form
+# The Upsample modules (this one and the VAE decoder's) run nearest-x2 + conv3x3 in the phase form: four 2x2 convs
+# over the zero-bordered low-res image, one per output parity (ops.PhaseConv, 4/9 of the FLOPs, no x2 image).
+# SD_AMD_UPSAMPLE_MATERIALISE=1 restores the previous route for A/B runs (the nearest-x2 image written
+# zero-bordered, a 3x3 conv over it with pad 0); SD_AMD_UPSAMPLE_FOLD=1 the upsample folded into the 3x3 conv's
+# DMA addresses.
 UPSAMPLE_FOLD = __import__("os").environ.get("SD_AMD_UPSAMPLE_FOLD", "0") == "1"
+UPSAMPLE_MATERIALISE = __import__("os").environ.get("SD_AMD_UPSAMPLE_MATERIALISE", "0") == "1"
+
+
+def upsample_phase_ok(x, padding=1):
+    """The phase form needs one NHWC source with whole 64-channel K blocks (and the conv's padding 1)."""
+    return not (UPSAMPLE_FOLD or UPSAMPLE_MATERIALISE) and not isinstance(x, tuple) and x.shape[-1] % 64 == 0 \
+        and padding == 1
 
 
 class Upsample(nn.Module):
-    """Reference ``model.py:100-131``: nearest x2 + conv3x3 (the upsample materialised zero-bordered, or folded
-    into the conv's loads)."""
+    """Reference ``model.py:100-131``: nearest x2 + conv3x3 (the phase form; else the upsample materialised
+    zero-bordered, or folded into the conv's loads)."""
 
     def __init__(self, channels, use_conv, dims=2, out_channels=None, padding=1):
         super().__init__()
@@ -108,10 +118,15 @@ class Upsample(nn.Module):
     def _prepare(self, dev):
         if self.use_conv:
             self._pc = ops.PackedConv([(self.conv.weight, self.channels)], self.conv.bias, device=dev)
+            self._ppc = None
+            if self.channels % 64 == 0 and self.padding == 1 and not (UPSAMPLE_FOLD or UPSAMPLE_MATERIALISE):
+                self._ppc = ops.PhaseConv(self.conv.weight, self.channels, self.conv.bias, device=dev)
 
     def _run(self, x):
         if not self.use_conv:
             return ops.group_norm_resample(x, None, "up")[1]
+        if getattr(self, "_ppc", None) is not None and upsample_phase_ok(x, self.padding):
+            return ops.conv2d(self._ppc, ops.zero_border(x, 1), phase=True, gn_stats=True)
         if UPSAMPLE_FOLD or isinstance(x, tuple) or x.shape[-1] % 8:
             return ops.conv2d(self._pc, x, upsample=True, pad=self.padding, gn_stats=True)
         return ops.conv2d(self._pc, ops.upsample_nearest2x_padded(x, self.padding), pad=0, gn_stats=True)

@@ -217,6 +217,43 @@ class PerImageWeights:
         self.w_batch_stride = weight.shape[1] * weight.shape[2]
 
 
+def fold_upsample_weight(w):
+    """The four 2x2 phase kernels of ``F.interpolate(scale_factor=2, mode="nearest")`` + conv3x3 pad 1.
+
+    Output pixel (2i+a, 2j+b) reads the low-res rows {i-1, i} (a = 0) or {i, i+1} (a = 1): of its three vertical
+    taps two land on the same low-res row, so their weights add (columns alike).  ``w`` [N, Cin, 3, 3] ->
+    [4, N, Cin, 2, 2] in w's dtype (phase = 2a + b; tap (dy, dx) multiplies low-res pixel (i-1+a+dy, j-1+b+dx),
+    zero outside the image).  Exact: sums only, in the dtype given (float32 for the packed weights, which are then
+    rounded to fp16 once)."""
+    assert w.dim() == 4 and w.shape[2:] == (3, 3)
+    rows = ((w[:, :, 0], w[:, :, 1] + w[:, :, 2]), (w[:, :, 0] + w[:, :, 1], w[:, :, 2]))     # [a][dy] -> [N, Cin, 3]
+    out = w.new_empty(4, w.shape[0], w.shape[1], 2, 2)
+    for a in range(2):
+        for dy in range(2):
+            r = rows[a][dy]
+            cols = ((r[:, :, 0], r[:, :, 1] + r[:, :, 2]), (r[:, :, 0] + r[:, :, 1], r[:, :, 2]))   # [b][dx]
+            for b in range(2):
+                for dx in range(2):
+                    out[2 * a + b, :, :, dy, dx] = cols[b][dx]
+    return out
+
+
+class PhaseConv:
+    """The packed weights of an Upsample's conv in the phase form (``conv2d(..., phase=True)``): the four 2x2
+    kernels of ``fold_upsample_weight`` (summed in fp32, rounded to fp16 once), each packed as a ``PackedConv``
+    matrix [roundup(N, 128)][4 * roundup(cin_src, 64)], stacked [4, ...] (``sdk_conv_args.weight_batch_stride``
+    apart).  Built once from the module's parameters."""
+
+    def __init__(self, weight, cin_src, bias=None, device="cuda"):
+        ph = fold_upsample_weight(weight.detach().float())
+        packs = [PackedConv([(ph[q], cin_src)], bias if q == 0 else None, device=device) for q in range(4)]
+        self.weight = torch.stack([pk.weight for pk in packs]).contiguous()
+        self.N, self.k_total, self.bias = packs[0].N, packs[0].k_total, packs[0].bias
+        self.geglu = False
+        self.seg_geom = [(2, cin_src)]
+        self.w_batch_stride = self.weight.shape[1] * self.weight.shape[2]
+
+
 def _conv_source_hash():
     import hashlib
     import os
@@ -429,7 +466,7 @@ def _conv2d_batch_chunks(pc, x, seg2, gn, row_bias, residual, out, B, kw):
 
 def conv2d(pc: PackedConv, x, *, ksize=None, stride=1, pad=None, pad_end=0, upsample=False, gn=None, silu=False,
            seg2=None, bias=True, row_bias=None, residual=None, out_mode=OUT_NHWC_F16, out=None,
-           variant=None, split_k=None, act=ACT_NONE, gn_stats=False, plan_out=None):
+           variant=None, split_k=None, act=ACT_NONE, gn_stats=False, plan_out=None, phase=False):
     """Run the implicit-GEMM conv.  ``seg2`` = (x2, gn2, silu2) adds a fused 1x1 K segment.
     ``pad_end`` adds zero rows/cols after the source (asymmetric (0,1,0,1) padding).
     ``row_bias`` = (fp32 tensor [B, ld], column offset) — the per-(batch, channel) add.
@@ -439,8 +476,13 @@ def conv2d(pc: PackedConv, x, *, ksize=None, stride=1, pad=None, pad_end=0, upsa
     consumed by ``group_norm``, which then skips its statistics pass).  ``plan_out``: a dict that
     receives the launched plan (``variant``, ``split_k``, ``grid_tiles``, ``gn_chunks`` of the
     ConvPlanInfo; host integers, so it is safe under graph capture; a conv that runs as batch
-    chunks reports its last chunk)."""
+    chunks reports its last chunk).  ``phase``: ``pc`` is a ``PhaseConv`` and ``x`` the low-res image with its
+    1-pixel zero border (``zero_border``): nearest-x2 + conv3x3 pad 1 as four 2x2 convs, the ordinary
+    [B, 2H, 2W, N] output (``sdk_conv_args.upsample_phase``)."""
     _claim(out)
+    if phase:
+        assert isinstance(pc, PhaseConv) and not isinstance(x, tuple) and not upsample and stride == 1
+        ksize, pad, pad_end = 2, 0, 0
     B0 = _as_pair(x)[0].shape[0]
     if B0 > 1 and (_src_bytes(x) >= BUF_LIMIT or (seg2 is not None and _src_bytes(seg2[0]) >= BUF_LIMIT)):
         if out is None:
@@ -450,13 +492,15 @@ def conv2d(pc: PackedConv, x, *, ksize=None, stride=1, pad=None, pad_end=0, upsa
             p_ = k_ // 2 if pad is None else pad
             Ho = (lh + 2 * p_ + pad_end - k_) // stride + 1
             Wo = (lw + 2 * p_ + pad_end - k_) // stride + 1
+            if phase:
+                Ho, Wo = 2 * (lh - 2), 2 * (lw - 2)
             shape = {OUT_NHWC_F16: (B0, Ho, Wo, pc.N), OUT_GEGLU_F16: (B0, Ho, Wo, pc.N // 2),
                      OUT_NCHW_F32: (B0, pc.N, Ho, Wo)}.get(out_mode, (B0, Ho, Wo, pc.N))
             dt = torch.float16 if out_mode in (OUT_NHWC_F16, OUT_GEGLU_F16) else torch.float32
             out = torch.empty(shape, dtype=dt, device=a0.device)
         kw = dict(ksize=ksize, stride=stride, pad=pad, pad_end=pad_end, upsample=upsample, silu=silu, bias=bias,
                   out_mode=out_mode, variant=variant, split_k=split_k, act=act, gn_stats=gn_stats,
-                  plan_out=plan_out)
+                  plan_out=plan_out, phase=phase)
         return _conv2d_batch_chunks(pc, x, seg2, gn, row_bias, residual, out, B0, kw)
     a = ConvArgs()
     k0 = pc.seg_geom[0][0] if ksize is None else ksize
@@ -467,6 +511,9 @@ def conv2d(pc: PackedConv, x, *, ksize=None, stride=1, pad=None, pad_end=0, upsa
     lh, lw = (2 * H, 2 * W) if upsample else (H, W)
     Ho = (lh + 2 * pad + pad_end - k0) // stride + 1
     Wo = (lw + 2 * pad + pad_end - k0) // stride + 1
+    if phase:
+        Ho, Wo = 2 * (H - 2), 2 * (W - 2)
+        a.upsample_phase = 1
     a.nseg = 1
     if seg2 is not None:
         x2, gn2, silu2 = seg2
@@ -658,6 +705,18 @@ def upsample_bilinear2x(x):
     B, H, W, Cc = x.shape
     y = torch.empty(B, 2 * H, 2 * W, Cc, dtype=torch.float16, device=x.device)
     check(lib().sdk_upsample_bilinear2x(_ptr(x), _ptr(y), B, H, W, Cc, _stream()), "upsample_bilinear2x")
+    return y
+
+
+def zero_border(x, pad=1):
+    """NHWC fp16 x inside a zero border of ``pad``: [B, H + 2pad, W + 2pad, C] (the source of the phase-form
+    Upsample conv, ``conv2d(..., phase=True)``)."""
+    _need_cuda(x, "zero_border")
+    B, H, W, Cc = x.shape
+    if x.stride(-1) != 1 or x.stride(1) != W * x.stride(2) or x.stride(0) != H * x.stride(1):
+        x = x.contiguous()
+    y = torch.empty(B, H + 2 * pad, W + 2 * pad, Cc, dtype=torch.float16, device=x.device)
+    check(lib().sdk_zero_border(_ptr(x), x.stride(2), _ptr(y), B, H, W, Cc, pad, _stream()), "zero_border")
     return y
 
 
