@@ -2686,124 +2686,181 @@ int launch_skinny(const Params& p, hipStream_t s) {
 
 #endif  // SDK_PART(0)
 
+template <class CF, int SIMPLE>
+int launch_glds_as(const Params& p, hipStream_t s) {
+  static std::atomic<unsigned long long> attr_set{0};   // per device: the dynamic-LDS cap, once
+  if (int e = ensure_dyn_lds((const void*)conv_glds_kernel<CF, SIMPLE>, CF::LDS_BYTES, attr_set, "conv2d")) return e;
+  hipLaunchKernelGGL((conv_glds_kernel<CF, SIMPLE>), dim3(p.tiles_m * p.tiles_n, p.split), dim3(CF::NT),
+                     CF::LDS_BYTES, s, p);
+  return check_launch("conv_glds");
+}
+
 template <class CF>
 int launch_glds(const Params& p, hipStream_t s) {
-  static std::atomic<unsigned long long> attr_set{0}, attr_simple{0};   // per device: the dynamic-LDS cap, once
-  if (p.simple == 1) {
-    if (int e = ensure_dyn_lds((const void*)conv_glds_kernel<CF, 1>, CF::LDS_BYTES, attr_simple, "conv2d")) return e;
-    hipLaunchKernelGGL((conv_glds_kernel<CF, 1>), dim3(p.tiles_m * p.tiles_n, p.split), dim3(CF::NT), CF::LDS_BYTES,
-                       s, p);
-    return check_launch("conv_glds");
+  switch (p.simple) {
+    case 1: return launch_glds_as<CF, 1>(p, s);
+    case 2: return launch_glds_as<CF, 2>(p, s);
+    default: return launch_glds_as<CF, 0>(p, s);
   }
-  if (p.simple == 2) {
-    static std::atomic<unsigned long long> attr_simple2{0};
-    if (int e = ensure_dyn_lds((const void*)conv_glds_kernel<CF, 2>, CF::LDS_BYTES, attr_simple2, "conv2d")) return e;
-    hipLaunchKernelGGL((conv_glds_kernel<CF, 2>), dim3(p.tiles_m * p.tiles_n, p.split), dim3(CF::NT), CF::LDS_BYTES,
-                       s, p);
-    return check_launch("conv_glds");
-  }
-  if (int e = ensure_dyn_lds((const void*)conv_glds_kernel<CF>, CF::LDS_BYTES, attr_set, "conv2d")) return e;
-  hipLaunchKernelGGL((conv_glds_kernel<CF>), dim3(p.tiles_m * p.tiles_n, p.split), dim3(CF::NT), CF::LDS_BYTES, s,
-                     p);
-  return check_launch("conv_glds");
+}
+
+// ---------------------------------------------------------------------- the variant table
+// One row per variant id; the planner, the part launchers, the dispatch of sdk_conv2d and sdk_kernel_name
+// all read it, and nothing else says what an id means.  A row's columns:
+//   id | kernel family | config type (its TBM x TBN is the tile) | DBG mask (DIAG only) |
+//   workgroups per CU for the planner's fill estimate (not Cfg::OCC: 4 shares a CU at OCC 1) |
+//   whether the epilogue pairs the (x, gate) halves of a GEGLU projection | sdk_kernel_name
+// The sublist a row sits in is the compile part that instantiates its kernel (below).  Families: NONE no such id;
+// IGEMM register-staged conv_igemm_kernel; GLDS the LDS-DMA tile conv_glds_kernel; PH32 / PH16 the phased 256x256
+// conv_ph_kernel on 32x32x16 / 16x16x32; DIRECT (<= 8 output channels); SKINNY (<= 64 rows); DIAG a phased
+// ablation (wrong outputs by design, launched by the diagnostics build only); RETIRED named, never planned.
+enum class Fam { NONE, IGEMM, GLDS, PH32, PH16, DIRECT, SKINNY, DIAG, RETIRED };
+struct CfgIgemm { static constexpr int TBM = BM, TBN = BN; };
+struct CfgUntiled { static constexpr int TBM = 0, TBN = 0; };   // direct / skinny: no BM x BN tiling
+template <class CF> struct TileOf { static constexpr int TBM = CF::TBM, TBN = CF::TBN; };
+template <int S, int D> struct TileOf<PhCfg<S, D>> { static constexpr int TBM = 256, TBN = 256; };
+
+// variant 5 (256x320 on 32x32x16, 16 waves) spilled at the 128-VGPR cap of 4 waves per SIMD; its row keeps the
+// name and carries the config of 22, the same tile on 16x16x32, which a forced 5 runs as.  36 / 37 (halo tiles)
+// and 39 (the 8-wave 256x320 on 32x32x16, spilled, never built) have no row: unknown.
+#define SDK_CONV_VARIANTS_P0(X, P)                                                                      \
+  X(P, 0, IGEMM, CfgIgemm, 0, 2, true, "conv_igemm_kernel")                                             \
+  X(P, 5, RETIRED, Cfg256x320m, 0, 1, false, "conv_glds_kernel<Cfg<256,320,8,2>>")                      \
+  X(P, 34, DIRECT, CfgUntiled, 0, 1, false, "conv_direct_kernel")                                       \
+  X(P, 35, SKINNY, CfgUntiled, 0, 1, false, "conv_skinny_kernel")
+#define SDK_CONV_VARIANTS_P1(X, P)                                                                      \
+  X(P, 2, GLDS, Cfg256x256, 0, 1, true, "conv_glds_kernel<Cfg<256,256,2,4>>")                           \
+  X(P, 3, GLDS, Cfg256x128, 0, 1, true, "conv_glds_kernel<Cfg<256,128,4,2>>")                           \
+  X(P, 4, GLDS, Cfg128x128, 0, 2, true, "conv_glds_kernel<Cfg<128,128,2,2>>")                           \
+  X(P, 6, GLDS, Cfg256x160, 0, 1, false, "conv_glds_kernel<Cfg<256,160,8,1>>")                          \
+  X(P, 7, GLDS, Cfg128x320, 0, 1, false, "conv_glds_kernel<Cfg<128,320,4,2>>")
+#define SDK_CONV_VARIANTS_P2(X, P)                                                                      \
+  X(P, 16, GLDS, Cfg128x128r4, 0, 1, true, "conv_glds_kernel<Cfg<128,128,2,2,4>>")                      \
+  X(P, 17, GLDS, Cfg256x128r3, 0, 1, true, "conv_glds_kernel<Cfg<256,128,4,2,3>>")                      \
+  X(P, 18, GLDS, Cfg128x128r3, 0, 1, true, "conv_glds_kernel<Cfg<128,128,2,2,3>>")                      \
+  X(P, 19, GLDS, Cfg128x256r3, 0, 1, true, "conv_glds_kernel<Cfg<128,256,2,4,3>>")                      \
+  X(P, 22, GLDS, Cfg256x320m, 0, 1, false, "conv_glds_kernel<Cfg<256,320,8,2,2,m16>>")                  \
+  X(P, 23, GLDS, Cfg128x320m, 0, 1, false, "conv_glds_kernel<Cfg<128,320,4,2,2,m16>>")
+#define SDK_CONV_VARIANTS_P3(X, P)                                                                      \
+  X(P, 24, GLDS, Cfg256x160m, 0, 1, false, "conv_glds_kernel<Cfg<256,160,8,1,2,m16>>")                  \
+  X(P, 25, GLDS, Cfg128x256r3m, 0, 1, true, "conv_glds_kernel<Cfg<128,256,2,4,3,m16>>")                 \
+  X(P, 26, GLDS, Cfg128x128r3m, 0, 1, true, "conv_glds_kernel<Cfg<128,128,2,2,3,m16>>")                 \
+  X(P, 31, GLDS, Cfg128x160o2m, 0, 2, false, "conv_glds_kernel<Cfg<128,160,4,1,2,m16,occ2>>")           \
+  X(P, 32, GLDS, Cfg128x128o2m, 0, 2, true, "conv_glds_kernel<Cfg<128,128,2,2,2,m16,occ2>>")            \
+  X(P, 33, GLDS, Cfg128x160r4m, 0, 1, false, "conv_glds_kernel<Cfg<128,160,4,1,4,m16>>")
+// the ablations are not named (sdk_kernel_name: "unknown"): no DMA, no MFMA, DMA from the zero page, no epilogue
+// stores, W / A from the zero page, no W / A DMA issued, A DMAs read W rows (cheap addressing, L2), A DMAs read
+// the centre tap (no masks / halo)
+#define SDK_CONV_VARIANTS_P4(X, P)                                                                      \
+  X(P, 8, PH32, PhCfg8, 0, 1, true, "conv_ph_kernel<256x256,ring8>")                                    \
+  X(P, 9, PH32, PhCfg10, 0, 1, true, "conv_ph_kernel<256x256,ring10>")                                  \
+  X(P, 20, PH16, PhCfg8, 0, 1, true, "conv_ph_kernel<256x256,ring8,m16>")                               \
+  X(P, 21, PH16, PhCfg10, 0, 1, true, "conv_ph_kernel<256x256,ring10,m16>")                             \
+  X(P, 10, DIAG, PhCfg8, 1, 1, true, "unknown")                                                         \
+  X(P, 11, DIAG, PhCfg8, 2, 1, true, "unknown")                                                         \
+  X(P, 12, DIAG, PhCfg8, 4, 1, true, "unknown")                                                         \
+  X(P, 13, DIAG, PhCfg8, 64, 1, true, "unknown")                                                        \
+  X(P, 14, DIAG, PhCfg8, 16, 1, true, "unknown")                                                        \
+  X(P, 15, DIAG, PhCfg8, 32, 1, true, "unknown")                                                        \
+  X(P, 27, DIAG, PhCfg8, 128, 1, true, "unknown")                                                       \
+  X(P, 28, DIAG, PhCfg8, 256, 1, true, "unknown")                                                       \
+  X(P, 29, DIAG, PhCfg8, 512, 1, true, "unknown")                                                       \
+  X(P, 30, DIAG, PhCfg8, 1024, 1, true, "unknown")
+// 8-wave 256-row tiles on 16x16x32 (64 / 128-row wave tiles)
+#define SDK_CONV_VARIANTS_P5(X, P)                                                                      \
+  X(P, 38, GLDS, Cfg256x320w8m, 0, 1, false, "conv_glds_kernel<Cfg<256,320,4,2,2,m16>>")                \
+  X(P, 40, GLDS, Cfg256x256w8m, 0, 1, true, "conv_glds_kernel<Cfg<256,256,2,4,2,m16>>")
+#define SDK_CONV_VARIANTS(X)                                                                            \
+  SDK_CONV_VARIANTS_P0(X, 0) SDK_CONV_VARIANTS_P1(X, 1) SDK_CONV_VARIANTS_P2(X, 2) SDK_CONV_VARIANTS_P3(X, 3) \
+  SDK_CONV_VARIANTS_P4(X, 4) SDK_CONV_VARIANTS_P5(X, 5)
+constexpr int kVariantIds = 41;      // ids are 0 .. 40 (a row past the end does not compile)
+constexpr int kRetiredRunsAs = 22;
+
+#ifdef SDK_CONV_DIAGNOSTICS
+constexpr bool kDiagnostics = true;
+#else
+constexpr bool kDiagnostics = false;
+#endif
+
+// A tile-kernel row's launch.  A template, so `if constexpr` keeps each row to its own family's kernel: a
+// kernel template is instantiated only in the part whose sublist names it.
+template <Fam F, class CF, int DBG>
+int launch_variant(const Params& p, hipStream_t s) {
+  if constexpr (F == Fam::GLDS) return launch_glds<CF>(p, s);
+  else if constexpr (F == Fam::PH32) return launch_ph<CF>(p, s);
+  else if constexpr (F == Fam::PH16) return launch_ph<CF, 0, true>(p, s);
+  else if constexpr (F == Fam::DIAG && kDiagnostics) return launch_ph<CF, DBG>(p, s);
+  else return fail(SDK_EINVAL, "conv2d: this build has no kernel for the planned variant");
 }
 
 // ---------------------------------------------------------------------- compile partition
 // build.py compiles this file once per part (-DSDK_CONV_PART=k, in parallel; one monolithic object took
-// ~10 minutes): part 0 holds the host planner, the ABI entry points and the small kernels, parts 1-4 the
+// ~10 minutes): part 0 holds the host planner, the ABI entry points and the small kernels, parts 1-5 the
 // tile-kernel instantiations, reached through these hidden C-linkage launchers (the kernel templates are
-// visible everywhere, each is instantiated only in the part whose launcher names it).  Without
+// visible everywhere, each is instantiated only in the part whose launcher expands its row).  Without
 // SDK_CONV_PART every part is in one object.
 #define SDK_HIDDEN __attribute__((visibility("hidden")))
 }  // namespace
 }  // namespace sdk
-extern "C" SDK_HIDDEN int sdk_conv_launch_part1(int v, const void* pp, int psize, void* st);
-extern "C" SDK_HIDDEN int sdk_conv_launch_part2(int v, const void* pp, int psize, void* st);
-extern "C" SDK_HIDDEN int sdk_conv_launch_part3(int v, const void* pp, int psize, void* st);
-extern "C" SDK_HIDDEN int sdk_conv_launch_part4(int v, const void* pp, int psize, void* st);
-extern "C" SDK_HIDDEN int sdk_conv_launch_part5(int v, const void* pp, int psize, void* st);
 // Params lives in an anonymous namespace, so each part compiles its own copy of the type: the caller passes
 // its sizeof(Params) and a part whose layout differs (a part-only preprocessor state) refuses the launch
-#define SDK_PART_FN(k) extern "C" SDK_HIDDEN int sdk_conv_launch_part##k(int v, const void* pp, int psize,       \
-                                                                    void* st) {                           \
-    using namespace sdk;                                                                                \
+#define SDK_PART_DECL(k) extern "C" SDK_HIDDEN int sdk_conv_launch_part##k(int v, const void* pp, int psize, void* st)
+#define SDK_LAUNCH_CASE(P, ID, FAM, CF, DBG, PER_CU, GEGLU, NAME) \
+    case ID: return launch_variant<Fam::FAM, CF, DBG>(p, s);
+#define SDK_PART_FN(k) SDK_PART_FN_(k)   /* k may itself be a macro (SDK_CONV_PART) */
+#define SDK_PART_FN_(k) SDK_PART_DECL(k) {                                                              \
+    using namespace sdk;                                                                               \
     if (psize != (int)sizeof(Params))                                                                   \
       return fail(SDK_EINVAL, "conv2d: Params layout differs between compile parts (" +                 \
                                   std::to_string(psize) + " vs " + std::to_string(sizeof(Params)) + ")"); \
     const Params& p = *static_cast<const Params*>(pp);                                                 \
     const hipStream_t s = (hipStream_t)st;                                                              \
-    switch (v) {
-#define SDK_PART_END                                                                                    \
-    }                                                                                                   \
+    switch (v) { SDK_CONV_VARIANTS_P##k(SDK_LAUNCH_CASE, k) }                                           \
     return fail(SDK_EINVAL, "conv2d: variant " + std::to_string(v) + " is not in this launcher part");  \
   }
-#if SDK_PART(1)
-SDK_PART_FN(1)
-    case 2: return launch_glds<Cfg256x256>(p, s);
-    case 3: return launch_glds<Cfg256x128>(p, s);
-    case 4: return launch_glds<Cfg128x128>(p, s);
-    case 6: return launch_glds<Cfg256x160>(p, s);
-    case 7: return launch_glds<Cfg128x320>(p, s);
-SDK_PART_END
-#endif
-#if SDK_PART(2)
-SDK_PART_FN(2)
-    case 16: return launch_glds<Cfg128x128r4>(p, s);
-    case 17: return launch_glds<Cfg256x128r3>(p, s);
-    case 18: return launch_glds<Cfg128x128r3>(p, s);
-    case 19: return launch_glds<Cfg128x256r3>(p, s);
-    case 22: return launch_glds<Cfg256x320m>(p, s);
-    case 23: return launch_glds<Cfg128x320m>(p, s);
-SDK_PART_END
-#endif
-#if SDK_PART(3)
-SDK_PART_FN(3)
-    case 24: return launch_glds<Cfg256x160m>(p, s);
-    case 25: return launch_glds<Cfg128x256r3m>(p, s);
-    case 26: return launch_glds<Cfg128x128r3m>(p, s);
-    case 31: return launch_glds<Cfg128x160o2m>(p, s);
-    case 32: return launch_glds<Cfg128x128o2m>(p, s);
-    case 33: return launch_glds<Cfg128x160r4m>(p, s);
-SDK_PART_END
-#endif
-#if SDK_PART(5)
-SDK_PART_FN(5)
-    case 38: return launch_glds<Cfg256x320w8m>(p, s);
-    case 40: return launch_glds<Cfg256x256w8m>(p, s);
-SDK_PART_END
-#endif
-#if SDK_PART(4)
-SDK_PART_FN(4)
-    case 8: return launch_ph<PhCfg8>(p, s);
-    case 9: return launch_ph<PhCfg10>(p, s);
-    case 20: return launch_ph<PhCfg8, 0, true>(p, s);    // phased 256x256, 16x16x32 MFMA
-    case 21: return launch_ph<PhCfg10, 0, true>(p, s);
-#ifdef SDK_CONV_DIAGNOSTICS
-    case 10: return launch_ph<PhCfg8, 1>(p, s);   // diagnostics: no DMA
-    case 11: return launch_ph<PhCfg8, 2>(p, s);   // diagnostics: no MFMA
-    case 12: return launch_ph<PhCfg8, 4>(p, s);   // diagnostics: DMA from the zero page
-    case 13: return launch_ph<PhCfg8, 64>(p, s);  // diagnostics: no epilogue stores
-    case 14: return launch_ph<PhCfg8, 16>(p, s);  // diagnostics: W from the zero page
-    case 15: return launch_ph<PhCfg8, 32>(p, s);  // diagnostics: A from the zero page
-    case 27: return launch_ph<PhCfg8, 128>(p, s);   // diagnostics: no W DMA issued
-    case 28: return launch_ph<PhCfg8, 256>(p, s);   // diagnostics: no A DMA issued
-    case 29: return launch_ph<PhCfg8, 512>(p, s);   // diagnostics: A DMAs read W rows (cheap addressing, L2)
-    case 30: return launch_ph<PhCfg8, 1024>(p, s);  // diagnostics: A DMAs read the centre tap (no masks/halo)
-#endif
-SDK_PART_END
+SDK_PART_DECL(1); SDK_PART_DECL(2); SDK_PART_DECL(3); SDK_PART_DECL(4); SDK_PART_DECL(5);
+#if SDK_CONV_PART > 0   // this object's own part
+SDK_PART_FN(SDK_CONV_PART)
+#elif SDK_CONV_PART < 0
+SDK_PART_FN(1) SDK_PART_FN(2) SDK_PART_FN(3) SDK_PART_FN(4) SDK_PART_FN(5)
 #endif
 #if SDK_PART(0)
 namespace sdk {
 namespace {
 
+struct Variant { Fam fam; int part, bm, bn, per_cu; bool geglu; const char* name; };
+struct VariantTable { Variant row[kVariantIds]; };
+constexpr VariantTable make_variant_table() {
+  VariantTable t{};
+#define SDK_ROW(P, ID, FAM, CF, DBG, PER_CU, GEGLU, NAME) \
+  t.row[ID] = Variant{Fam::FAM, P, TileOf<CF>::TBM, TileOf<CF>::TBN, PER_CU, GEGLU, NAME};
+  SDK_CONV_VARIANTS(SDK_ROW)
+#undef SDK_ROW
+  return t;
+}
+constexpr VariantTable kVariants = make_variant_table();
+// the row of an id, nullptr when there is none
+inline const Variant* variant_row(int v) {
+  return v >= 0 && v < kVariantIds && kVariants.row[v].fam != Fam::NONE ? &kVariants.row[v] : nullptr;
+}
+constexpr int variant_of(Fam f) {   // the id of a one-kernel family
+  for (int v = 0; v < kVariantIds; ++v)
+    if (kVariants.row[v].fam == f) return v;
+  return -1;
+}
+constexpr int kIgemm = variant_of(Fam::IGEMM), kDirect = variant_of(Fam::DIRECT), kSkinny = variant_of(Fam::SKINNY);
+// the phase form's row map and the in-launch split live in conv_glds_kernel (and the split-K reduces)
+inline bool lds_dma_tile(const Variant& r) { return r.fam == Fam::GLDS; }
+// the fp16 epilogues that emit GroupNorm statistics without a split: conv_glds_kernel's and the phased 32x32x16 one
+inline bool emits_gn_stats(const Variant& r) { return r.fam == Fam::GLDS || r.fam == Fam::PH32; }
+using PartLaunch = int (*)(int, const void*, int, void*);
+constexpr PartLaunch kPartLaunch[] = {nullptr, sdk_conv_launch_part1, sdk_conv_launch_part2, sdk_conv_launch_part3,
+                                      sdk_conv_launch_part4, sdk_conv_launch_part5};
+
 #ifdef SDK_CONV_DIAGNOSTICS
 unsigned long long* g_conv_stamps = nullptr;   // 8 stamps x 65536 workgroups (SDK_CONV_STAMPS=1)
 constexpr int kStampWgs = 65536;
-constexpr bool kDiagnostics = true;
-#else
-constexpr bool kDiagnostics = false;
 #endif
-inline bool is_diagnostic_variant(int v) { return (v >= 10 && v <= 15) || (v >= 27 && v <= 30); }
 // benchmark override of the tile configuration, read once when the library loads
 const int g_env_variant = [] {
   const char* fe = getenv("SDK_CONV_VARIANT");
@@ -2816,6 +2873,16 @@ int tile_group_m(const sdk_conv_args* a, const Params& p) {
   static const int env_gm = getenv("SDK_CONV_GM") ? atoi(getenv("SDK_CONV_GM")) : 0;
   const int g = a->tile_group_m > 0 ? a->tile_group_m : env_gm > 0 ? env_gm : 1;
   return std::max(1, std::min(g, p.tiles_m));
+}
+
+// the plan of the direct and skinny kernels: one launch of `grid` workgroups, no split, no workspace, no
+// GroupNorm statistics
+void plan_untiled(Params& p, sdk_conv_plan_info* info, int variant, int tiles_n, int grid, int kt, double kreal) {
+  p.variant = variant; p.split = 1; p.tiles_m = 1; p.tiles_n = tiles_n; p.Npad = p.N; p.kt_per_split = kt;
+  if (info) {
+    info->split_k = 1; info->grid_tiles = grid; info->workspace_bytes = 0; info->variant = variant;
+    info->flops = 2.0 * p.M * (double)p.N * kreal; info->gn_chunks = 0;
+  }
 }
 
 int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
@@ -2930,12 +2997,10 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
   // tile configuration: LDS-DMA kernels for transform-free operands, scored by
   // padded-work efficiency x whole-chip wave quantisation x measured per-config
   // throughput
-  struct Opt { int variant, bm, bn, nw; double pref; bool geglu_ok; };
+  struct Opt { int variant; double pref; };
   // relative throughput of each config on shapes it tiles exactly (tools/bench_conv.py, MI355X)
-  const Opt opts[] = {{8, 256, 256, 8, 1.05, true}, {2, 256, 256, 8, 1.00, true}, {22, 256, 320, 16, 0.92, false},
-                      {7, 128, 320, 8, 0.88, false}, {6, 256, 160, 8, 0.72, false},
-                      {4, 128, 128, 4, 0.72, true}, {3, 256, 128, 8, 0.65, true}};
-  int var = 0, tbm = BM, tbn = BN, best_split = 0;
+  const Opt opts[] = {{8, 1.05}, {2, 1.00}, {22, 0.92}, {7, 0.88}, {6, 0.72}, {4, 0.72}, {3, 0.65}};
+  int var = kIgemm, best_split = 0;
   auto pick_split = [&](int tiles, int slots, double& fill) {
     int best = 1;
     double bf = -1;
@@ -2952,29 +3017,25 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
   };
   if (p.wbs && transform) return fail(SDK_EINVAL, "conv2d: per-image weights need a transform-free operand");
   if (phase && p.simple != 1) return fail(SDK_EINVAL, "conv2d: the phase form runs on the linear A issue only");
-  // the phase form's row map lives in conv_glds_kernel (its fp16 epilogues) and the split-K reduces
-  auto phase_capable = [](int v) {
-    return (v >= 2 && v <= 7 && v != 5) || (v >= 16 && v <= 19) || (v >= 22 && v <= 26) || (v >= 31 && v <= 33) ||
-           v == 38 || v == 40;
-  };
   if (!transform) {
     double best = -1;
     for (const Opt& o : opts) {
-      if (a->out_mode == SDK_OUT_GEGLU_F16 && !o.geglu_ok) continue;
-      if (phase ? !phase_capable(o.variant) : (p.wbs && p.hw_out % o.bm)) continue;   // per-image weights: M-tiles inside one image
-      const int tmm = phase ? 4 * ((p.ph_rows + o.bm - 1) / o.bm) : (p.M + o.bm - 1) / o.bm;
-      const int tnn = (p.N + o.bn - 1) / o.bn;
-      const double eff = (double)p.M * p.N / ((double)tmm * o.bm * tnn * o.bn);
+      const Variant& r = kVariants.row[o.variant];
+      if (a->out_mode == SDK_OUT_GEGLU_F16 && !r.geglu) continue;
+      if (phase ? !lds_dma_tile(r) : (p.wbs && p.hw_out % r.bm)) continue;   // per-image weights: M-tiles inside one image
+      const int tmm = phase ? 4 * ((p.ph_rows + r.bm - 1) / r.bm) : (p.M + r.bm - 1) / r.bm;
+      const int tnn = (p.N + r.bn - 1) / r.bn;
+      const double eff = (double)p.M * p.N / ((double)tmm * r.bm * tnn * r.bn);
       double fill;
       const bool can_split = a->out_mode != SDK_OUT_GEGLU_F16 && a->cout % 8 == 0;
-      const int per = (o.variant == 4) ? 2 : 1;
-      const int sp = can_split ? pick_split(tmm * tnn, 256 * per, fill) : 1;
+      const int slots = 256 * r.per_cu;
+      const int sp = can_split ? pick_split(tmm * tnn, slots, fill) : 1;
       if (!can_split) {
-        const int slots = 256 * per, blocks = tmm * tnn;
+        const int blocks = tmm * tnn;
         fill = (double)blocks / ((double)((blocks + slots - 1) / slots) * slots);
       }
       const double score = eff * fill * o.pref;
-      if (score > best) { best = score; var = o.variant; tbm = o.bm; tbn = o.bn; best_split = sp; }
+      if (score > best) { best = score; var = o.variant; best_split = sp; }
     }
   }
   // forced configuration: the caller's autotuner (variant_hint = 1 + id) or, for
@@ -2987,21 +3048,9 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
                            g.stride == 1 && !g.upsample && g.pad_end == 0 && g.pad <= 1 && g.c_split == g.cin &&
                            g.gn_scale == nullptr && !g.silu && !a->residual && !a->row_bias &&
                            a->act == SDK_ACT_NONE && a->out_mode != SDK_OUT_GEGLU_F16 && !p.wbs;
-    if (forced == 34 && !direct_ok) return fail(SDK_EINVAL, "conv2d: variant 34 (direct) does not fit this conv");
-    if (direct_ok && (forced < 0 || forced == 34)) {
-      p.variant = 34;
-      p.split = 1;
-      p.tiles_m = p.tiles_n = 1;
-      p.Npad = p.N;
-      p.kt_per_split = kt;
-      if (info) {
-        info->split_k = 1;
-        info->grid_tiles = ((a->wo + DC_TX - 1) / DC_TX) * ((a->ho + 7) / 8) * a->batch;
-        info->workspace_bytes = 0;
-        info->variant = 34;
-        info->flops = 2.0 * p.M * (double)p.N * kreal;
-        info->gn_chunks = 0;
-      }
+    if (forced == kDirect && !direct_ok) return fail(SDK_EINVAL, "conv2d: variant 34 (direct) does not fit this conv");
+    if (direct_ok && (forced < 0 || forced == kDirect)) {
+      plan_untiled(p, info, kDirect, 1, ((a->wo + DC_TX - 1) / DC_TX) * ((a->ho + 7) / 8) * a->batch, kt, kreal);
       if (a->gn_partial) return fail(SDK_EINVAL, "conv2d: the direct variant emits no GroupNorm statistics");
       return SDK_OK;
     }
@@ -3013,70 +3062,44 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
                            g.pad_end == 0 && !g.upsample && g.c_split == g.cin && g.gn_scale == nullptr &&
                            (a->out_mode == SDK_OUT_NHWC_F16 || a->out_mode == SDK_OUT_ROWS_F32) && !a->gn_partial &&
                            !p.wbs;
-    if (forced == 35 && !skinny_ok) return fail(SDK_EINVAL, "conv2d: variant 35 (skinny) does not fit this GEMM");
-    if (skinny_ok && (forced < 0 || forced == 35)) {
-      p.variant = 35;
-      p.split = 1;
-      p.tiles_m = 1;
-      p.tiles_n = (p.N + 15) / 16;
-      p.Npad = p.N;
-      p.kt_per_split = kt;
-      if (info) {
-        info->split_k = 1;
-        info->grid_tiles = p.tiles_n;
-        info->workspace_bytes = 0;
-        info->variant = 35;
-        info->flops = 2.0 * p.M * (double)p.N * kreal;
-        info->gn_chunks = 0;
-      }
+    if (forced == kSkinny && !skinny_ok) return fail(SDK_EINVAL, "conv2d: variant 35 (skinny) does not fit this GEMM");
+    if (skinny_ok && (forced < 0 || forced == kSkinny)) {
+      plan_untiled(p, info, kSkinny, (p.N + 15) / 16, (p.N + 15) / 16, kt, kreal);
       return SDK_OK;
     }
   }
-  // ids: 0 register-staged; 2..7 LDS-DMA configs; 8, 9 phased 256x256; 10..15 diagnostics;
-  // 16..19 deep-ring LDS-DMA configs; 20, 21 phased 256x256 on v_mfma_f32_16x16x32_f16;
-  // 22..26 LDS-DMA configs 256x320, 7, 6, 19, 18 on v_mfma_f32_16x16x32_f16 (5 retired); 27..30 diagnostics;
-  // 31, 32 two-per-CU 128x160 / 128x128 (16x16x32); 33 128x160 with a 4-stage ring; 34 direct (<= 8 outputs);
-  // 38 8-wave 256x320, 40 8-wave 256x256 (16x16x32, 64 / 128-row wave tiles; 39, the 256x320 on 32x32x16, spilled
-  // and is not built).
-  // The diagnostic ablations compute wrong outputs by design: the product library rejects them,
-  // only the separate diagnostics build (-DSDK_CONV_DIAGNOSTICS, libsdk_amd_diag.so) runs them.
-  if (is_diagnostic_variant(forced) && !kDiagnostics)
+  // What a forced id means is its row of the variant table.  The diagnostic ablations compute wrong outputs by
+  // design: the product library rejects them, only the separate diagnostics build (-DSDK_CONV_DIAGNOSTICS,
+  // libsdk_amd_diag.so) runs them.
+  const Variant* fr = variant_row(forced);
+  if (fr && fr->fam == Fam::DIAG && !kDiagnostics)
     return fail(SDK_EINVAL, "conv2d: variant " + std::to_string(forced) +
                                 " is a diagnostic ablation (only in libsdk_amd_diag.so)");
-  if (forced == 1 || (forced > 35 && forced < 38) || forced == 39 || forced > 40)
-    return fail(SDK_EINVAL, "conv2d: unknown variant " + std::to_string(forced));
-  // variant 5 (256x320 on 32x32x16, 16 waves) spilled at the 128-VGPR cap of 4 waves per SIMD — scratch VMEM
-  // ops under hand-counted vmcnt waits; variant 22 is the same tile on 16x16x32 without spills, so a forced 5
-  // (a leftover SDK_CONV_VARIANT=5 or an old tuning entry) runs as 22, with a one-time warning
-  if (forced == 5) {
+  if (forced >= 0 && !fr) return fail(SDK_EINVAL, "conv2d: unknown variant " + std::to_string(forced));
+  // a forced 5 (a leftover SDK_CONV_VARIANT=5 or an old tuning entry) runs as 22, the same 256x320 tile on 16x16x32
+  // (which is not spill-free either: 8 to 16 B/lane of scratch in build*/resource_usage.txt), with a one-time warning
+  if (fr && fr->fam == Fam::RETIRED) {
     static std::atomic<bool> warned{false};
     if (!warned.exchange(true))
       fprintf(stderr, "sd_amd conv2d: variant 5 is retired; running the same 256x320 tile as variant 22\n");
-    forced = 22;
+    forced = kRetiredRunsAs;
+    fr = &kVariants.row[forced];
   }
-  const int fbase = forced;
-  const bool fvalid = forced >= 0 && forced != 1 && (forced <= 33 || forced == 38 || forced == 40);
-  const bool fgeglu = (fbase <= 4 || fbase >= 8) && fbase != 22 && fbase != 23 && fbase != 24 && fbase != 31 &&
-                      fbase != 33 && fbase != 38;
-  if (fvalid && (forced == 0 || !transform) && (fgeglu || a->out_mode != SDK_OUT_GEGLU_F16)) {
-    static const int fbm[41] = {128, 0, 256, 256, 128, 256, 256, 128, 256, 256, 256, 256, 256, 256, 256, 256, 128,
-                                256, 128, 128, 256, 256, 256, 128, 256, 128, 128, 256, 256, 256, 256, 128, 128, 128,
-                                0, 0, 0, 0, 256, 256, 256};
-    static const int fbn[41] = {128, 0, 256, 128, 128, 320, 160, 320, 256, 256, 256, 256, 256, 256, 256, 256, 128,
-                                128, 128, 256, 256, 256, 320, 320, 160, 256, 128, 256, 256, 256, 256, 160, 128, 160,
-                                0, 0, 0, 0, 320, 320, 256};
-    if (phase ? phase_capable(forced) : (!p.wbs || (forced != 0 && p.hw_out % fbm[fbase] == 0))) {
-      var = forced;
-      tbm = fbm[fbase];
-      tbn = fbn[fbase];
-      best_split = 0;
-    }
+  // honoured when the kernel can run this conv: the register-staged kernel takes every operand but per-image
+  // weights, the others need a transform-free one, a GEGLU-pairing epilogue for the GEGLU output, the LDS-DMA
+  // tile family for the phase form, and per-image weights need M-tiles inside one image
+  if (fr && (fr->fam == Fam::IGEMM || !transform) && (fr->geglu || a->out_mode != SDK_OUT_GEGLU_F16) &&
+      (phase ? lds_dma_tile(*fr) : (!p.wbs || (fr->fam != Fam::IGEMM && p.hw_out % fr->bm == 0)))) {
+    var = forced;
+    best_split = 0;
   }
+  const Variant& row = kVariants.row[var];
+  const int tbm = row.bm, tbn = row.bn;
   if (phase) {
-    if (!phase_capable(var)) return fail(SDK_EINVAL, "conv2d: the phase form found no LDS-DMA tile plan");
+    if (!lds_dma_tile(row)) return fail(SDK_EINVAL, "conv2d: the phase form found no LDS-DMA tile plan");
     p.ph_rows_pad = (p.ph_rows + tbm - 1) / tbm * tbm;   // no M-tile straddles two phases
     p.M = 4 * p.ph_rows_pad;
-  } else if (p.wbs && (var == 0 || p.hw_out % tbm)) {
+  } else if (p.wbs && (row.fam == Fam::IGEMM || p.hw_out % tbm)) {
     return fail(SDK_EINVAL, "conv2d: per-image weights: no LDS-DMA tile fits inside one image");
   }
   p.variant = var;
@@ -3084,14 +3107,13 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
   p.tiles_n = (p.N + tbn - 1) / tbn;
   p.Npad = p.tiles_n * tbn;                       // split-K slab row stride
   const int tiles = p.tiles_m * p.tiles_n;
-  const int per_cu = (var == 0 || var == 4 || var == 31 || var == 32) ? 2 : 1;
   int split = a->split_k;
   if (split <= 0) {
     if (best_split > 0) {
       split = best_split;
     } else {
       split = 1;
-      while (tiles * split < 256 * per_cu && kt / (split * 2) >= 8 && split < 16) split *= 2;
+      while (tiles * split < 256 * row.per_cu && kt / (split * 2) >= 8 && split < 16) split *= 2;
     }
   }
   if (a->out_mode == SDK_OUT_GEGLU_F16 || a->cout % 8) split = 1;
@@ -3110,10 +3132,8 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
 #endif
   int64_t ws = split > 1 ? (int64_t)split * p.M * p.Npad * 4 : 0;
   if (a->split_inlaunch) {
-    const bool tile_kernel = (var >= 2 && var <= 7) || (var >= 16 && var <= 19) || (var >= 22 && var <= 26) ||
-                             (var >= 31 && var <= 33) || var == 38 || var == 40;
-    if (!tile_kernel)
-      return fail(SDK_EINVAL, "conv2d: in-launch split-K needs an LDS-DMA tile plan (variants 2-7, 16-19, 22-26, 31-33, 38, 40)");
+    if (!lds_dma_tile(row))
+      return fail(SDK_EINVAL, "conv2d: in-launch split-K needs an LDS-DMA tile plan (a conv_glds_kernel variant)");
     if (split != 2) return fail(SDK_EINVAL, "conv2d: in-launch split-K combines exactly two K halves (split_k = 2)");
     if (!a->tile_counters) return fail(SDK_EINVAL, "conv2d: in-launch split-K needs tile_counters");
     if (tiles > SDK_TILE_COUNTERS) return fail(SDK_EINVAL, "conv2d: in-launch split-K: more tiles than counters");
@@ -3136,13 +3156,11 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
   // GroupNorm statistics of the output: chunks per image the plan can emit (0 = none).  Split-K: the
   // reduce kernel, 64-row chunks (one chunk when hw_out is not a multiple of 64); otherwise the
   // LDS-DMA kernels' fp16 epilogue, one chunk per M-tile when tiles do not straddle images.
-  const bool glds = (var >= 2 && var <= 9) || (var >= 16 && var <= 19) || (var >= 22 && var <= 26) ||
-                    (var >= 31 && var <= 33) || var == 38 || var == 40;   // 8 / 9: the phased kernel's 32x32x16 epilogue
   int gn_nch = 0;
   if (a->out_mode == SDK_OUT_NHWC_F16) {
     const int hw_img = (phase ? 4 : 1) * p.hw_out;   // output pixels of one image
     if (split > 1 && !p.inl) gn_nch = hw_img % 64 == 0 ? hw_img / 64 : 1;
-    else if (glds && p.hw_out % tbm == 0) gn_nch = hw_img / tbm;   // in-launch split: the combining tile emits
+    else if (emits_gn_stats(row) && p.hw_out % tbm == 0) gn_nch = hw_img / tbm;   // in-launch: the combining tile emits
   }
   if (info) info->gn_chunks = gn_nch;
   if (a->gn_partial) {
@@ -3159,6 +3177,11 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
 
 using namespace sdk;
 
+extern "C" const char* sdk_kernel_name(int32_t variant) {
+  const Variant* r = variant_row(variant);
+  return r ? r->name : "unknown";
+}
+
 extern "C" int sdk_conv2d_plan(const sdk_conv_args* a, sdk_conv_plan_info* info) {
   Params p;
   return build_params(a, p, info);
@@ -3173,20 +3196,17 @@ extern "C" int sdk_conv2d(const sdk_conv_args* a, sdk_stream_t stream) {
     return fail(SDK_EWORKSPACE, "conv2d: split-K workspace too small");
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(p.tiles_m * p.tiles_n, p.split);
-  switch (p.variant) {
-    case 2: case 3: case 4: case 6: case 7: rc = sdk_conv_launch_part1(p.variant, &p, (int)sizeof(Params), s); break;
-    case 16: case 17: case 18: case 19: case 22: case 23: rc = sdk_conv_launch_part2(p.variant, &p, (int)sizeof(Params), s); break;
-    case 24: case 25: case 26: case 31: case 32: case 33: rc = sdk_conv_launch_part3(p.variant, &p, (int)sizeof(Params), s); break;
-    case 8: case 9: case 20: case 21: case 10: case 11: case 12: case 13: case 14: case 15: case 27: case 28:
-    case 29: case 30:
-      rc = sdk_conv_launch_part4(p.variant, &p, (int)sizeof(Params), s);
-      break;
-    case 38: case 40: rc = sdk_conv_launch_part5(p.variant, &p, (int)sizeof(Params), s); break;
-    case 34: rc = launch_direct(p, s); break;
-    case 35: rc = launch_skinny(p, s); break;
-    default:
+  const Variant& row = kVariants.row[p.variant];   // build_params plans ids of the table only
+  switch (row.fam) {
+    case Fam::IGEMM:
       hipLaunchKernelGGL(conv_igemm_kernel, grid, dim3(NT), 0, s, p);
       rc = check_launch("conv_igemm");
+      break;
+    case Fam::DIRECT: rc = launch_direct(p, s); break;
+    case Fam::SKINNY: rc = launch_skinny(p, s); break;
+    default:   // the tile kernels, each in its compile part (part 0 rows have no launcher: never planned)
+      rc = row.part ? kPartLaunch[row.part](p.variant, &p, (int)sizeof(Params), s)
+                    : fail(SDK_EINVAL, "conv2d: planned variant " + std::to_string(p.variant) + " has no kernel");
   }
   if (rc) return rc;
   if (p.inl) return SDK_OK;   // combined inside the launch

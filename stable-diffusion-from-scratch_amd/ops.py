@@ -464,6 +464,19 @@ def _conv2d_batch_chunks(pc, x, seg2, gn, row_bias, residual, out, B, kw):
     return full
 
 
+def _conv_out(pc, x, ksize, stride, pad, pad_end, upsample, phase, out_mode):
+    """(Ho, Wo, shape, dtype) of the output of a conv2d call."""
+    B, H, W = _as_pair(x)[0].shape[:3]
+    lh, lw = (2 * H, 2 * W) if upsample else (H, W)
+    Ho = (lh + 2 * pad + pad_end - ksize) // stride + 1
+    Wo = (lw + 2 * pad + pad_end - ksize) // stride + 1
+    if phase:
+        Ho, Wo = 2 * (H - 2), 2 * (W - 2)
+    shape = {OUT_GEGLU_F16: (B, Ho, Wo, pc.N // 2), OUT_NCHW_F32: (B, pc.N, Ho, Wo)}.get(out_mode, (B, Ho, Wo, pc.N))
+    dt = torch.float16 if out_mode in (OUT_NHWC_F16, OUT_GEGLU_F16) else torch.float32
+    return Ho, Wo, shape, dt
+
+
 def conv2d(pc: PackedConv, x, *, ksize=None, stride=1, pad=None, pad_end=0, upsample=False, gn=None, silu=False,
            seg2=None, bias=True, row_bias=None, residual=None, out_mode=OUT_NHWC_F16, out=None,
            variant=None, split_k=None, act=ACT_NONE, gn_stats=False, plan_out=None, phase=False):
@@ -484,36 +497,22 @@ def conv2d(pc: PackedConv, x, *, ksize=None, stride=1, pad=None, pad_end=0, upsa
         assert isinstance(pc, PhaseConv) and not isinstance(x, tuple) and not upsample and stride == 1
         ksize, pad, pad_end = 2, 0, 0
     B0 = _as_pair(x)[0].shape[0]
+    dev = _as_pair(x)[0].device
+    k0 = pc.seg_geom[0][0] if ksize is None else ksize
+    Ho, Wo, shape, dt = _conv_out(pc, x, k0, stride, k0 // 2 if pad is None else pad, pad_end, upsample, phase, out_mode)
     if B0 > 1 and (_src_bytes(x) >= BUF_LIMIT or (seg2 is not None and _src_bytes(seg2[0]) >= BUF_LIMIT)):
         if out is None:
-            a0 = _as_pair(x)[0]
-            lh, lw = (2 * a0.shape[1], 2 * a0.shape[2]) if upsample else (a0.shape[1], a0.shape[2])
-            k_ = pc.seg_geom[0][0] if ksize is None else ksize
-            p_ = k_ // 2 if pad is None else pad
-            Ho = (lh + 2 * p_ + pad_end - k_) // stride + 1
-            Wo = (lw + 2 * p_ + pad_end - k_) // stride + 1
-            if phase:
-                Ho, Wo = 2 * (lh - 2), 2 * (lw - 2)
-            shape = {OUT_NHWC_F16: (B0, Ho, Wo, pc.N), OUT_GEGLU_F16: (B0, Ho, Wo, pc.N // 2),
-                     OUT_NCHW_F32: (B0, pc.N, Ho, Wo)}.get(out_mode, (B0, Ho, Wo, pc.N))
-            dt = torch.float16 if out_mode in (OUT_NHWC_F16, OUT_GEGLU_F16) else torch.float32
-            out = torch.empty(shape, dtype=dt, device=a0.device)
+            out = torch.empty(shape, dtype=dt, device=dev)
         kw = dict(ksize=ksize, stride=stride, pad=pad, pad_end=pad_end, upsample=upsample, silu=silu, bias=bias,
                   out_mode=out_mode, variant=variant, split_k=split_k, act=act, gn_stats=gn_stats,
                   plan_out=plan_out, phase=phase)
         return _conv2d_batch_chunks(pc, x, seg2, gn, row_bias, residual, out, B0, kw)
     a = ConvArgs()
-    k0 = pc.seg_geom[0][0] if ksize is None else ksize
     if pad is None:
         pad = k0 // 2
     B, H, W = _fill_src(a.seg[0], x, k0, stride, pad, upsample, gn, silu)
     a.seg[0].pad_end = pad_end
-    lh, lw = (2 * H, 2 * W) if upsample else (H, W)
-    Ho = (lh + 2 * pad + pad_end - k0) // stride + 1
-    Wo = (lw + 2 * pad + pad_end - k0) // stride + 1
-    if phase:
-        Ho, Wo = 2 * (H - 2), 2 * (W - 2)
-        a.upsample_phase = 1
+    a.upsample_phase = 1 if phase else 0
     a.nseg = 1
     if seg2 is not None:
         x2, gn2, silu2 = seg2
@@ -529,16 +528,8 @@ def conv2d(pc: PackedConv, x, *, ksize=None, stride=1, pad=None, pad_end=0, upsa
         rb, off = row_bias
         a.row_bias = rb.data_ptr() + 4 * off
         a.row_bias_ld = rb.stride(0)
-    dev = (x[0] if isinstance(x, tuple) else x).device
     if out is None:
-        if out_mode == OUT_NHWC_F16:
-            out = torch.empty(B, Ho, Wo, pc.N, dtype=torch.float16, device=dev)
-        elif out_mode == OUT_GEGLU_F16:
-            out = torch.empty(B, Ho, Wo, pc.N // 2, dtype=torch.float16, device=dev)
-        elif out_mode == OUT_NCHW_F32:
-            out = torch.empty(B, pc.N, Ho, Wo, dtype=torch.float32, device=dev)
-        else:
-            out = torch.empty(B, Ho, Wo, pc.N, dtype=torch.float32, device=dev)
+        out = torch.empty(shape, dtype=dt, device=dev)
     a.out = out.data_ptr()
     a.out_ld = out.shape[-1] if out_mode != OUT_NCHW_F32 else 0
     a.out_mode = out_mode

@@ -87,6 +87,65 @@ def test_conv_plan_picks_skinny_and_names_every_variant(sdk):
     assert L.sdk_conv2d_plan(C.byref(a), C.byref(info)) != 0         # unknown id
 
 
+def test_conv_plans_equal_the_recorded_golden(sdk):
+    """The host planner decides what tests/golden/conv_plans.npz recorded, row for row: return code, variant,
+    split, grid, workspace, GroupNorm chunks and FLOPs over every variant id x split request x statistics request
+    of make_golden_conv_plans.CASES, and sdk_kernel_name for ids -1..48 (error text is not compared)."""
+    import make_golden_conv_plans as G
+    from sd_amd import _lib
+    assert "SDK_CONV_VARIANT" not in os.environ
+    want = np.load(G.OUT)
+    got = G.sweep(sdk.library(), _lib)
+    assert len(want["rc"]) == len(G.CASES) * len(G.HINTS) * len(G.SPLITS) * 2
+    assert sorted(want.files) == sorted(got)
+    for k in want.files:
+        bad = np.flatnonzero(want[k] != got[k])
+        assert bad.size == 0, (k, [(G.CASE_NAMES[got["case"][i]], int(got["hint"][i]), G.SPLITS[got["split_req"][i]],
+                                    int(got["gn_req"][i]), want[k][i], got[k][i]) for i in bad[:5]]
+                               if len(want[k]) == len(want["rc"]) else (want[k].tolist(), got[k].tolist()))
+    G.check_coverage(got)
+
+
+def _gemm_args(_lib, M, N, K, out_mode=0):
+    a = _lib.ConvArgs()
+    a.batch, a.ho, a.wo, a.cout, a.nseg = 1, M, 1, N, 1
+    s = a.seg[0]
+    s.src0 = 0x1000; s.c_split = K; s.cin = K; s.ld0 = K; s.h = M; s.w = 1
+    s.ksize = 1; s.stride = 1; s.pad = 0
+    a.weight = 0x2000; a.out = 0x3000; a.k_total = K
+    a.out_mode, a.out_ld, a.split_k = out_mode, (N // 2 if out_mode == 2 else N), 1
+    return a
+
+
+def test_hand_kept_variant_lists_agree_with_the_library(sdk):
+    """The lists that stay hand-kept outside csrc/conv.hip's variant table fail here when they drift from it:
+    the autotuner's candidates are the named ids minus the register-staged fallback and the retired 5; every
+    id of the exact tests' re-declared TILE is honoured with that tile's grid, and under the GEGLU output
+    exactly the ids of their GEGLU_OK are honoured."""
+    import conv_exact_util as U
+    from sd_amd import _lib, ops
+    L = sdk.library()
+    L.sdk_kernel_name.restype = C.c_char_p
+    named = {v for v in range(-1, 64) if L.sdk_kernel_name(v) != b"unknown"}
+    assert set(ops.AUTOTUNE.VARIANTS) == named - {0, 5}
+    info = _lib.ConvPlanInfo()
+    for v, (bm, bn) in U.TILE.items():
+        a = _gemm_args(_lib, 600, 704, 128)
+        a.variant_hint = v + 1
+        assert L.sdk_conv2d_plan(C.byref(a), C.byref(info)) == 0, (v, L.sdk_last_error())
+        assert info.variant == v and info.grid_tiles == -(-600 // bm) * -(-704 // bn), (v, info.variant, info.grid_tiles)
+        a = _gemm_args(_lib, 600, 704, 128, out_mode=2)
+        a.variant_hint = v + 1
+        assert L.sdk_conv2d_plan(C.byref(a), C.byref(info)) == 0, (v, L.sdk_last_error())
+        assert (info.variant == v) == (v in U.GEGLU_OK), (v, info.variant)
+
+
+def test_committed_tuning_cache_matches_the_conv_source(sdk):
+    """configs/conv_tuning_mi355x.json is keyed by the hash of csrc/conv.hip: a stale key loads nothing."""
+    from sd_amd import ops
+    assert ops._Autotune().load(os.path.join(ROOT, "configs", "conv_tuning_mi355x.json")) > 0
+
+
 def test_group_norm_workspace(sdk):
     L = sdk.library()
     assert L.sdk_group_norm_workspace(2, 4096, 320) > 0
