@@ -245,6 +245,30 @@ typedef struct {
 
 int sdk_attention(const sdk_attention_args* a, sdk_stream_t stream);
 
+/* The same launch with the kernel form chosen by the caller and read back (tests and tools;
+ * sdk_attention(a, s) is sdk_attention_form(a, SDK_ATTN_AUTO, NULL, s)).
+ *   SDK_ATTN_AUTO      the default of the head dim: 4 waves for head_dim <= 32 and > 80, 8 waves for
+ *                      40..48, 8 waves staggered for 56..80; the environment's tuning knobs apply
+ *                      (SDK_ATTN_NW=4, SDK_ATTN_STAG=0/1, SDK_ATTN_QB=2, read once per process)
+ *   SDK_ATTN_NW4       4 waves = 128 query rows per workgroup; every head_dim
+ *   SDK_ATTN_NW8       8 waves = 256 query rows; head_dim 40..80
+ *   SDK_ATTN_NW8_STAG  8 waves, waves 4..7 run half a key tile behind waves 0..3 (three LDS stages);
+ *                      head_dim 40..80
+ *   SDK_ATTN_QB2       4 waves with two 32-row query blocks each; head_dim 40..48, non-causal
+ * A form other than AUTO that has no instantiation at a->head_dim (or QB2 with a->causal) returns
+ * SDK_EINVAL; it never falls back to another form.
+ * ran (may be NULL) receives what was launched, from the launched kernel's template arguments: form (the
+ * form after AUTO is resolved), dqk / dv (the padded head dim of the QK^T and the PV products), waves per
+ * workgroup, qblocks (32-row query blocks per wave), stagger, seed_col (head_dim 40 with 8 waves: the
+ * padding column of Q that carries the running max; else 0), causal and grid (workgroups).  The causal
+ * kernels are neither staggered nor seeded through a column, so a causal launch reports stagger = 0 and
+ * seed_col = 0 under every form.  ran is written on the host before the launch: it costs nothing and is
+ * the same under stream capture. */
+enum { SDK_ATTN_AUTO = 0, SDK_ATTN_NW4, SDK_ATTN_NW8, SDK_ATTN_NW8_STAG, SDK_ATTN_QB2 };
+typedef struct { int32_t form, dqk, dv, waves, qblocks, stagger, seed_col, causal, grid; } sdk_attention_form_info;
+int sdk_attention_form(const sdk_attention_args* a, int32_t form, sdk_attention_form_info* ran /* may be NULL */,
+                       sdk_stream_t stream);
+
 /* Fused cross-attention block on a cached context K|V: out = (softmax(scale * (t Wq^T)_h K_h^T) V_h)_h
  * Wo^T + bias + res, one kernel, q and o kept in LDS.  Replaces, per denoising step, the
  * to_q Linear + flash_attn_func + to_out Linear of CrossAttention.forward with a context

@@ -50,6 +50,11 @@ class AttentionArgs(C.Structure):
                 ("scale", f32), ("causal", i32)]
 
 
+class AttentionFormInfo(C.Structure):
+    _fields_ = [("form", i32), ("dqk", i32), ("dv", i32), ("waves", i32), ("qblocks", i32), ("stagger", i32),
+                ("seed_col", i32), ("causal", i32), ("grid", i32)]
+
+
 class XAttnArgs(C.Structure):
     _fields_ = [("t", vp), ("kv", vp), ("wq", vp), ("wo", vp), ("bias", vp), ("res", vp), ("out", vp),
                 ("t_ld", i32), ("kv_ld", i32), ("w_ld", i32), ("res_ld", i32), ("out_ld", i32), ("batch", i32),
@@ -96,10 +101,11 @@ class ConcatArgs(C.Structure):
 
 OUT_NHWC_F16, OUT_NCHW_F32, OUT_GEGLU_F16, OUT_ROWS_F32 = 0, 1, 2, 3
 ACT_NONE, ACT_QUICK_GELU = 0, 1
+ATTN_AUTO, ATTN_NW4, ATTN_NW8, ATTN_NW8_STAG, ATTN_QB2 = range(5)
 RESAMPLE_AVGPOOL2, RESAMPLE_NEAREST2 = 0, 1
 
 EXPORTS = ["sdk_conv2d_plan", "sdk_conv2d", "sdk_group_norm_workspace", "sdk_group_norm_affine", "sdk_group_norm_apply", "sdk_group_norm_apply_padded", "sdk_group_norm_apply_ex", "sdk_group_norm", "sdk_group_norm_finalize", "sdk_layer_norm",
-           "sdk_attention", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_posterior_step", "sdk_masked_q_sample", "sdk_concat_nchw_to_nhwc", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
+           "sdk_attention", "sdk_attention_form", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_posterior_step", "sdk_masked_q_sample", "sdk_concat_nchw_to_nhwc", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
            "sdk_diag_gaussian_sample", "sdk_stochastic_encode", "sdk_token_embedding", "sdk_extract_patches",
            "sdk_fold_patches", "sdk_vq_code_norms", "sdk_vq_nearest_splits", "sdk_vq_nearest", "sdk_vq_lookup", "sdk_vq_remap",
            "sdk_upsample_bilinear2x", "sdk_upsample_nearest2x_padded", "sdk_zero_border", "sdk_gelu",
@@ -140,6 +146,7 @@ def lib():
     L.sdk_gelu.argtypes = [vp, vp, i64, vp]
     L.sdk_layer_norm.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, f32, vp]
     L.sdk_attention.argtypes = [C.POINTER(AttentionArgs), vp]
+    L.sdk_attention_form.argtypes = [C.POINTER(AttentionArgs), i32, C.POINTER(AttentionFormInfo), vp]
     L.sdk_cross_attention_block_supported.argtypes = [i32, i32, i32, i32]
     L.sdk_xattn_pack_weight.argtypes = [vp, i32, vp, i32, vp]
     L.sdk_cross_attention_block.argtypes = [C.POINTER(XAttnArgs), vp]

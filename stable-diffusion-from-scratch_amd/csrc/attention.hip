@@ -269,7 +269,9 @@ __global__ void __launch_bounds__(NW * 64, (STAG && DQK <= 64) ? 4 : QB == 2 ? 1
           dm = -(float)mh - m_run[qb];
           if (fh == ((QSD & 15) >> 3)) qf[qb][QSD >> 4][QSD & 7] = mh;
         }
-        const float alpha = fast_exp2(-dm);
+        // tile 0 has nothing to rescale (o = l = 0), and exp2(-m) overflows for a first-tile max below
+        // -128: 0 * inf would poison the row
+        const float alpha = t == 0 ? 1.f : fast_exp2(-dm);
         l_run[qb] *= alpha;
 #pragma unroll
         for (int db = 0; db < DV / 32; ++db)
@@ -375,21 +377,73 @@ __global__ void __launch_bounds__(NW * 64, (STAG && DQK <= 64) ? 4 : QB == 2 ? 1
   }
 }
 
+// ``ran`` (may be NULL) is filled here, from the template arguments of the kernel that is launched,
+// on the host and before the launch (the same under graph capture); its ``form`` is the caller's
 template <int DQK, int DV, int NW, int QB, bool STAG = false, int QSD = 0>
-int launch(const AttnParams& p, hipStream_t s) {
+int launch(const AttnParams& p, hipStream_t s, sdk_attention_form_info* ran) {
   constexpr int ROWS = 32 * QB * NW;
   const long long blocks = (long long)((p.nq + ROWS - 1) / ROWS) * p.heads * p.batch;
   if (blocks > 0x7fffffffLL) return fail(SDK_EINVAL, "attention: grid too large");
   dim3 grid((unsigned)blocks);
   if (p.causal) {
     if constexpr (QB == 1) {   // the CLIP text tower's head sizes; other forms are not instantiated
+      if (ran) *ran = sdk_attention_form_info{ran->form, DQK, DV, NW, QB, 0, 0, 1, (int32_t)blocks};
       hipLaunchKernelGGL((attn_fwd_kernel<DQK, DV, NW, QB, true>), grid, dim3(NW * 64), 0, s, p);
       return check_launch("attn_fwd_causal");
     }
     return fail(SDK_EINVAL, "attention: causal needs the one-block-per-wave form");
   }
+  if (ran) *ran = sdk_attention_form_info{ran->form, DQK, DV, NW, QB, STAG ? 1 : 0, QSD, 0, (int32_t)blocks};
   hipLaunchKernelGGL((attn_fwd_kernel<DQK, DV, NW, QB, false, STAG, QSD>), grid, dim3(NW * 64), 0, s, p);
   return check_launch("attn_fwd");
+}
+
+// The form -> instantiation mapping, once: the first row with the form and dmin <= d <= dmax runs.
+// A (form, d) pair without a row has no instantiation.
+struct AttnInst {
+  int form, dmin, dmax;
+  int (*run)(const AttnParams&, hipStream_t, sdk_attention_form_info*);
+};
+const AttnInst ATTN_TABLE[] = {
+    {SDK_ATTN_NW4, 8, 16, launch<16, 32, 4, 1>},
+    {SDK_ATTN_NW4, 24, 32, launch<32, 32, 4, 1>},
+    {SDK_ATTN_NW4, 40, 48, launch<48, 64, 4, 1>},
+    {SDK_ATTN_NW4, 56, 64, launch<64, 64, 4, 1>},
+    {SDK_ATTN_NW4, 72, 80, launch<80, 96, 4, 1>},
+    {SDK_ATTN_NW4, 88, 96, launch<96, 96, 4, 1>},
+    {SDK_ATTN_NW4, 104, 128, launch<128, 128, 4, 1>},
+    {SDK_ATTN_NW4, 136, 160, launch<160, 160, 4, 1>},
+    {SDK_ATTN_NW8, 40, 40, launch<48, 64, 8, 1, false, 40>},   // -m in Q's padding column 40
+    {SDK_ATTN_NW8, 40, 48, launch<48, 64, 8, 1>},
+    {SDK_ATTN_NW8, 56, 64, launch<64, 64, 8, 1>},
+    {SDK_ATTN_NW8, 72, 80, launch<80, 96, 8, 1>},              // 165 vs 189 VGPRs
+    {SDK_ATTN_NW8_STAG, 40, 40, launch<48, 64, 8, 1, true, 40>},
+    {SDK_ATTN_NW8_STAG, 40, 48, launch<48, 64, 8, 1, true>},
+    {SDK_ATTN_NW8_STAG, 56, 64, launch<64, 64, 8, 1, true>},
+    {SDK_ATTN_NW8_STAG, 72, 80, launch<80, 96, 8, 1, true>},
+    {SDK_ATTN_QB2, 40, 48, launch<48, 64, 4, 2>},              // non-causal only (launch)
+};
+
+// SDK_ATTN_AUTO: the default form of a head dim, with the tuning knobs of the environment
+int auto_form(int d) {
+  // one 32-row query block per wave at 3-4 waves per SIMD; SDK_ATTN_QB=2 selects two blocks per
+  // wave at one wave per SIMD (shared K/V fragments; measured 1.6x slower at d = 40 under hipcc's
+  // scheduling, kept as a tuning knob)
+  static const int qb2 = getenv("SDK_ATTN_QB") && atoi(getenv("SDK_ATTN_QB")) == 2;
+  // d <= 80: 8-wave workgroups (half the staging registers: d = 40 127 VGPRs = 4 waves per SIMD,
+  // 547 vs 623 us for the 4-wave form at SD-1's 64x64 level); SDK_ATTN_NW=4 selects the latter.
+  // d = 160 keeps 4 waves: at 256 query rows one 8-wave group per head would idle half the CUs
+  static const int nw4 = getenv("SDK_ATTN_NW") && atoi(getenv("SDK_ATTN_NW")) == 4;
+  // SDK_ATTN_STAG=1: the 8-wave forms with the lag half staggered by half a tile (three stages).  Default on
+  // for 48 < d <= 80 (same-box A/Bs: d = 64 975 vs 1060 us at SD-2's 96x96 level, d = 40 582 vs 521 us,
+  // profiles/r3_attn_stag_ab.txt; d = 80 at SD-1's 32x32 level 67.1-67.5 vs 69.3 us, profiles/r5_attn80_ab.txt);
+  // SDK_ATTN_STAG=0 / 1 forces it off / on everywhere
+  static const int stag_env = getenv("SDK_ATTN_STAG") ? atoi(getenv("SDK_ATTN_STAG")) : -1;
+  if (d <= 32 || d > 80) return SDK_ATTN_NW4;
+  if (d <= 48 && qb2) return SDK_ATTN_QB2;
+  if (nw4) return SDK_ATTN_NW4;
+  const int stag = stag_env == 1 || (stag_env < 0 && d > 48);
+  return stag ? SDK_ATTN_NW8_STAG : SDK_ATTN_NW8;
 }
 
 }  // namespace
@@ -398,6 +452,11 @@ int launch(const AttnParams& p, hipStream_t s) {
 using namespace sdk;
 
 extern "C" int sdk_attention(const sdk_attention_args* a, sdk_stream_t stream) {
+  return sdk_attention_form(a, SDK_ATTN_AUTO, nullptr, stream);
+}
+
+extern "C" int sdk_attention_form(const sdk_attention_args* a, int32_t form, sdk_attention_form_info* ran,
+                                  sdk_stream_t stream) {
   if (!a || !a->q || !a->k || !a->v || !a->o) return fail(SDK_EINVAL, "attention: null pointer");
   if (a->head_dim <= 0 || a->head_dim % 8 || a->head_dim > 160)
     return fail(SDK_EINVAL, "attention: head_dim must be a multiple of 8 in [8, 160]");
@@ -413,32 +472,13 @@ extern "C" int sdk_attention(const sdk_attention_args* a, sdk_stream_t stream) {
                a->scale * 1.4426950408889634f, a->causal ? 1 : 0};
   hipStream_t s = (hipStream_t)stream;
   const int d = a->head_dim;
-  // one 32-row query block per wave at 3-4 waves per SIMD; SDK_ATTN_QB=2 selects two blocks per
-  // wave at one wave per SIMD (shared K/V fragments; measured 1.6x slower at d = 40 under hipcc's
-  // scheduling, kept as a tuning knob)
-  static const int qb2 = getenv("SDK_ATTN_QB") && atoi(getenv("SDK_ATTN_QB")) == 2;
-  if (d <= 16) return launch<16, 32, 4, 1>(p, s);
-  if (d <= 32) return launch<32, 32, 4, 1>(p, s);
-  // d <= 80: 8-wave workgroups (half the staging registers: d = 40 127 VGPRs = 4 waves per SIMD,
-  // 547 vs 623 us for the 4-wave form at SD-1's 64x64 level); SDK_ATTN_NW=4 selects the latter.
-  // d = 160 keeps 4 waves: at 256 query rows one 8-wave group per head would idle half the CUs
-  static const int nw4 = getenv("SDK_ATTN_NW") && atoi(getenv("SDK_ATTN_NW")) == 4;
-  // SDK_ATTN_STAG=1: the 8-wave forms with the lag half staggered by half a tile (three stages).  Default on
-  // for 48 < d <= 80 (same-box A/Bs: d = 64 975 vs 1060 us at SD-2's 96x96 level, d = 40 582 vs 521 us,
-  // profiles/r3_attn_stag_ab.txt; d = 80 at SD-1's 32x32 level 67.1-67.5 vs 69.3 us, profiles/r5_attn80_ab.txt);
-  // SDK_ATTN_STAG=0 / 1 forces it off / on everywhere
-  static const int stag_env = getenv("SDK_ATTN_STAG") ? atoi(getenv("SDK_ATTN_STAG")) : -1;
-  const int stag = stag_env == 1 || (stag_env < 0 && d > 48 && d <= 80);
-  if (d <= 48)
-    return qb2 ? launch<48, 64, 4, 2>(p, s)
-           : nw4  ? launch<48, 64, 4, 1>(p, s)
-           : d == 40 ? (stag ? launch<48, 64, 8, 1, true, 40>(p, s) : launch<48, 64, 8, 1, false, 40>(p, s))
-           : stag ? launch<48, 64, 8, 1, true>(p, s) : launch<48, 64, 8, 1>(p, s);
-  if (d <= 64)
-    return nw4 ? launch<64, 64, 4, 1>(p, s) : stag ? launch<64, 64, 8, 1, true>(p, s) : launch<64, 64, 8, 1>(p, s);
-  if (d <= 80)   // 165 vs 189 VGPRs
-    return nw4 ? launch<80, 96, 4, 1>(p, s) : stag ? launch<80, 96, 8, 1, true>(p, s) : launch<80, 96, 8, 1>(p, s);
-  if (d <= 96) return launch<96, 96, 4, 1>(p, s);
-  if (d <= 128) return launch<128, 128, 4, 1>(p, s);
-  return launch<160, 160, 4, 1>(p, s);
+  if (form < SDK_ATTN_AUTO || form > SDK_ATTN_QB2) return fail(SDK_EINVAL, "attention: unknown form");
+  const int f = form == SDK_ATTN_AUTO ? auto_form(d) : form;
+  for (const AttnInst& e : ATTN_TABLE)
+    if (e.form == f && d >= e.dmin && d <= e.dmax) {
+      if (ran) ran->form = f;
+      return e.run(p, s, ran);
+    }
+  return fail(SDK_EINVAL, "attention: this form has no instantiation at this head_dim (8 waves and the staggered "
+                          "form: 40..80; two blocks per wave: 40..48)");
 }

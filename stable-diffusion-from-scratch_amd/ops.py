@@ -987,9 +987,17 @@ def probe_peaks(reps=3):
 
 # --------------------------------------------------------------------------- attention
 
-def attention(q, k, v, *, batch, heads, nq, nk, head_dim, scale, out=None, causal=False):
+ATTN_FORMS = {"auto": _lib.ATTN_AUTO, "nw4": _lib.ATTN_NW4, "nw8": _lib.ATTN_NW8, "nw8_stag": _lib.ATTN_NW8_STAG,
+              "qb2": _lib.ATTN_QB2}
+_ATTN_FORM_NAMES = {v: k for k, v in ATTN_FORMS.items()}
+
+
+def attention(q, k, v, *, batch, heads, nq, nk, head_dim, scale, out=None, causal=False, form=None, form_out=None):
     """q/k/v: 2-D fp16 views [batch*n, ld] (head h at columns h*head_dim...); ``causal`` masks
-    key j > query i."""
+    key j > query i.  ``form``: None / "auto" (the head dim's default) or "nw4" / "nw8" / "nw8_stag" /
+    "qb2" (``sdk_attention_form``; a form without an instantiation at this head dim raises).
+    ``form_out``: a dict that receives the launched kernel's form and template arguments (host
+    integers, filled before the launch; the same under graph capture)."""
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         _need_cuda(t, "attention " + n)
     if out is None:
@@ -1002,7 +1010,15 @@ def attention(q, k, v, *, batch, heads, nq, nk, head_dim, scale, out=None, causa
     a.causal = 1 if causal else 0
     if PROFILER.active:
         PROFILER.begin("attention", (batch, heads, nq, nk, head_dim))
-    check(lib().sdk_attention(C.byref(a), _stream()), "attention")
+    if form is None and form_out is None:
+        check(lib().sdk_attention(C.byref(a), _stream()), "attention")
+    else:
+        info = _lib.AttentionFormInfo()
+        check(lib().sdk_attention_form(C.byref(a), ATTN_FORMS[form or "auto"], C.byref(info), _stream()), "attention")
+        if form_out is not None:
+            form_out.update(form=_ATTN_FORM_NAMES[info.form], dqk=info.dqk, dv=info.dv, waves=info.waves,
+                            qblocks=info.qblocks, stagger=info.stagger, seed_col=info.seed_col,
+                            causal=info.causal, grid=info.grid)
     if PROFILER.active:
         PROFILER.end()
     return out

@@ -1,4 +1,6 @@
-"""Attention kernel microbenchmark on the SD-1 / SD-2 / VAE shapes (random data, HIP events)."""
+"""Attention kernel microbenchmark on the SD-1 / SD-2 / VAE shapes (random data, HIP events).
+``--form nw4|nw8|nw8_stag|qb2`` runs that kernel form (sdk_attention_form) where the head dim has it and skips the
+other shapes; the launched form is printed either way."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,7 +16,12 @@ SHAPES = [  # name, B, heads, nq, nk, d
     ("sd2_self_96x96_d64", 8, 5, 9216, 9216, 64),
     ("vae_mid_64x64_d64", 16, 8, 4096, 4096, 64),
 ]
-ONLY = sys.argv[1:]          # optional shape-name filter (profiling one kernel)
+ARGS = sys.argv[1:]
+FORM = None
+if "--form" in ARGS:
+    FORM = ARGS[ARGS.index("--form") + 1]
+    del ARGS[ARGS.index("--form"):ARGS.index("--form") + 2]
+ONLY = ARGS                  # optional shape-name filter (profiling one kernel)
 REPS = int(os.environ.get("BENCH_REPS", "5"))
 for name, B, H, nq, nk, d in SHAPES:
     if ONLY and name not in ONLY:
@@ -22,8 +29,16 @@ for name, B, H, nq, nk, d in SHAPES:
     q = torch.randn(B * nq, H * d, device="cuda").half()
     k = torch.randn(B * nk, H * d, device="cuda").half()
     v = torch.randn(B * nk, H * d, device="cuda").half()
-    f = lambda: ops.attention(q, k, v, batch=B, heads=H, nq=nq, nk=nk, head_dim=d, scale=d ** -0.5)
-    f()
+    ran = {}
+    f = lambda: ops.attention(q, k, v, batch=B, heads=H, nq=nq, nk=nk, head_dim=d, scale=d ** -0.5, form=FORM,
+                              form_out=ran)
+    try:
+        f()
+    except RuntimeError as e:
+        if FORM is None or "no instantiation" not in str(e):
+            raise
+        print(f"{name:24s} no {FORM} form at d = {d}")
+        continue
     torch.cuda.synchronize()
     ts = []
     for _ in range(REPS):
@@ -37,4 +52,4 @@ for name, B, H, nq, nk, d in SHAPES:
     ms = sorted(ts)[len(ts) // 2]
     fl = 4.0 * B * H * nq * nk * d
     byt = 2.0 * (B * nq * H * d * 2 + 2 * B * nk * H * d)
-    print(f"{name:24s} {ms*1000:9.1f} us  {fl/ms/1e9:8.1f} TFLOP/s  {byt/ms/1e6:8.1f} GB/s")
+    print(f"{name:24s} {ms*1000:9.1f} us  {fl/ms/1e9:8.1f} TFLOP/s  {byt/ms/1e6:8.1f} GB/s  {ran['form']}")
