@@ -573,6 +573,34 @@ int sdk_group_norm_resample(const sdk_group_norm_args* a, int32_t mode, int32_t 
 int sdk_embedding_add(const void* emb, const float* table, const int64_t* ids, void* out, int32_t batch, int32_t dim,
                       int32_t n, sdk_stream_t stream);
 
+/* ---------------------------------------------------------------- condition encoders (clip_encoder/modules.py)
+ * Row gather of ClassEmbedder (clip_encoder/modules.py:37-45: embedding(batch[key][:, None])):
+ * out[i][:] = fp16(table[ids[i]][:]); ids int64 [n], table fp32 [rows][dim], out fp16 [n][dim], any dim >= 1.
+ * 16-byte accesses when dim % 8 == 0 and table / out are 16-byte aligned, scalar otherwise.  The caller
+ * range-checks ids on the host (as for sdk_vq_lookup). */
+int sdk_embedding_rows(const int64_t* ids, const float* table, void* out, int32_t n, int32_t dim,
+                       sdk_stream_t stream);
+
+/* SpatialRescaler's F.interpolate(x, scale_factor=s, mode=...) (clip_encoder/modules.py:197-205) on NCHW fp32
+ * with torch's defaults: align_corners=False, no antialias, the given scale factor used for the coordinates
+ * (source step (float)(1 / s)), out = floor(in * s) per axis (checked: any other out_h / out_w is
+ * SDK_EINVAL).  x [planes][h][w] -> y [planes][out_h][out_w], planes = batch * channels.
+ *   SDK_RESIZE_NEAREST   src = min(floor(dst * step), in - 1)                      (torch's legacy "nearest")
+ *   SDK_RESIZE_BILINEAR  src = max(step * (dst + 0.5) - 0.5, 0); wy0*(wx0*p00 + wx1*p01) + wy1*(wx0*p10 + wx1*p11)
+ *   SDK_RESIZE_BICUBIC   src = step * (dst + 0.5) - 0.5, A = -0.75, border taps clamped; rows combined as above
+ *   SDK_RESIZE_AREA      adaptive average: rows [floor(o*in/out), ceil((o+1)*in/out)), sum / kh / kw
+ * Weights, coordinates and sums in fp32 in the order torch's CPU kernels evaluate them, no contraction.
+ * One thread per output element, consecutive lanes on consecutive output columns. */
+enum { SDK_RESIZE_NEAREST = 0, SDK_RESIZE_BILINEAR = 1, SDK_RESIZE_BICUBIC = 2, SDK_RESIZE_AREA = 3 };
+typedef struct {
+  const float* x;
+  float* y;
+  int32_t planes, h, w, out_h, out_w, mode;
+  double scale_h, scale_w;
+} sdk_resize2d_args;
+
+int sdk_resize2d(const sdk_resize2d_args* a, sdk_stream_t stream);
+
 /* ---------------------------------------------------------------- introspection */
 const char* sdk_last_error(void);
 int sdk_version(void);

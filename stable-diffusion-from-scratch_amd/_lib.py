@@ -99,7 +99,13 @@ class ConcatArgs(C.Structure):
                 ("c_pad", i32)]
 
 
+class Resize2dArgs(C.Structure):
+    _fields_ = [("x", vp), ("y", vp), ("planes", i32), ("h", i32), ("w", i32), ("out_h", i32), ("out_w", i32),
+                ("mode", i32), ("scale_h", C.c_double), ("scale_w", C.c_double)]
+
+
 OUT_NHWC_F16, OUT_NCHW_F32, OUT_GEGLU_F16, OUT_ROWS_F32 = 0, 1, 2, 3
+RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_BICUBIC, RESIZE_AREA = range(4)
 ACT_NONE, ACT_QUICK_GELU = 0, 1
 ATTN_AUTO, ATTN_NW4, ATTN_NW8, ATTN_NW8_STAG, ATTN_QB2 = range(5)
 RESAMPLE_AVGPOOL2, RESAMPLE_NEAREST2 = 0, 1
@@ -109,7 +115,7 @@ EXPORTS = ["sdk_conv2d_plan", "sdk_conv2d", "sdk_group_norm_workspace", "sdk_gro
            "sdk_diag_gaussian_sample", "sdk_stochastic_encode", "sdk_token_embedding", "sdk_extract_patches",
            "sdk_fold_patches", "sdk_vq_code_norms", "sdk_vq_nearest_splits", "sdk_vq_nearest", "sdk_vq_lookup", "sdk_vq_remap",
            "sdk_upsample_bilinear2x", "sdk_upsample_nearest2x_padded", "sdk_zero_border", "sdk_gelu",
-           "sdk_group_norm_film", "sdk_group_norm_resample", "sdk_embedding_add", "sdk_last_error", "sdk_version", "sdk_kernel_name",
+           "sdk_group_norm_film", "sdk_group_norm_resample", "sdk_embedding_add", "sdk_embedding_rows", "sdk_resize2d", "sdk_last_error", "sdk_version", "sdk_kernel_name",
            "sdk_probe_mfma_flops", "sdk_probe_mfma", "sdk_probe_copy", "sdk_probe_copy_ex"]
 
 _lib = None
@@ -140,6 +146,8 @@ def lib():
                                       i32, vp]
     L.sdk_group_norm_resample.argtypes = [C.POINTER(GroupNormArgs), i32, i32, i32, i32, i32, vp, vp, vp]
     L.sdk_embedding_add.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+    L.sdk_embedding_rows.argtypes = [vp, vp, vp, i32, i32, vp]
+    L.sdk_resize2d.argtypes = [C.POINTER(Resize2dArgs), vp]
     L.sdk_upsample_bilinear2x.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     L.sdk_upsample_nearest2x_padded.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, vp]
     L.sdk_zero_border.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, vp]

@@ -10,7 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsdk_amd.so")
-SOURCES = ["conv.hip", "norm.hip", "attention.hip", "sampler.hip", "xattn.hip", "ff.hip", "token.hip", "vq.hip", "probe.hip"]
+SOURCES = ["conv.hip", "norm.hip", "attention.hip", "sampler.hip", "xattn.hip", "ff.hip", "token.hip", "vq.hip", "cond.hip",
+           "probe.hip"]
 # conv.hip is compiled once per part (its SDK_CONV_PART partition: host planner + small kernels, then the tile
 # kernel instantiations in four groups) so the objects build in parallel
 CONV_PARTS = 6

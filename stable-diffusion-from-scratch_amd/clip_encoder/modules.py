@@ -17,6 +17,13 @@ network, which this build never has: ``version`` may be a LOCAL directory (confi
 model.safetensors, vocab.json + merges.txt); otherwise the ViT-L/14 text configuration is built
 with uninitialised weights and ``forward(text)`` needs a local tokenizer — ``encode_tokens(ids)``
 takes ids directly.
+
+The other condition encoders of the reference's file (``modules.py:25-209``) are mirrored as well: ``ClassEmbedder``
+(one ``sdk_embedding_rows`` launch → a one-token fp16 context), ``TransformerEmbedder`` / ``BERTTokenizer`` /
+``BERTEmbedder`` (the HIP encoder of ``x_transformer.py``; the BERT tokenizer from a LOCAL ``vocab.txt``) and
+``SpatialRescaler`` (``sdk_resize2d`` per stage, then the optional 1x1 ``channel_mapper`` on the library's conv).
+The abstract method is ``encode`` (the reference spells it ``encoder``); ``FrozenClipImageEmbedder`` is not mirrored
+(it needs the ``clip`` package and hub weights), so ``clip`` and ``kornia`` are not imported.
 """
 from __future__ import annotations
 
@@ -38,6 +45,165 @@ class AbstractEncoder(nn.Module):
 
     def encode(self, *args, **kwargs):
         raise NotImplementedError
+
+
+class ClassEmbedder(nn.Module):
+    """Reference ``clip_encoder/modules.py:25-45``: the class label as a one-token cross-attention context.
+    ``forward(batch)`` gathers ``embedding.weight[batch[key]]`` with ``sdk_embedding_rows`` → fp16
+    [B, 1, embed_dim] on the GPU (the UNet's context dtype)."""
+
+    def __init__(self, embed_dim, n_classes=1000, key="class"):
+        super().__init__()
+        self.key = key
+        self.embedding = nn.Embedding(n_classes, embed_dim)
+
+    @torch.no_grad()
+    def forward(self, batch, key=None):
+        if key is None:
+            key = self.key
+        ids = batch[key]
+        w = self.embedding.weight
+        if not torch.is_tensor(ids) or not ids.is_cuda or not w.is_cuda:
+            raise TypeError("sd_amd.ClassEmbedder: HIP path only — move the module and the labels to the GPU")
+        if ids.dim() != 1 or ids.dtype not in (torch.int64, torch.int32):
+            raise ValueError(f"sd_amd.ClassEmbedder: labels must be integer [B], got {ids.dtype} {tuple(ids.shape)}")
+        try:
+            rows = ops.embedding_rows(ids.to(torch.int64), w.detach().float())
+        except ValueError as e:
+            raise ValueError(f"sd_amd.ClassEmbedder: label outside [0, {w.shape[0]})") from e
+        return rows[:, None, :]
+
+
+class TransformerEmbedder(AbstractEncoder):
+    """Some transformer encoder layers (reference ``clip_encoder/modules.py:48-73``): token ids
+    [B, T <= max_seq_len] → fp16 [B, T, n_embed] on the HIP encoder of ``x_transformer.py``."""
+
+    def __init__(self, n_embed, n_layer, vocab_size, max_seq_len=77, device="cuda"):
+        super().__init__()
+        from .x_transformer import Encoder, TransformerWrapper
+        self.device = device
+        self.transformer = TransformerWrapper(num_tokens=vocab_size, max_seq_len=max_seq_len,
+                                              attn_layers=Encoder(dim=n_embed, depth=n_layer))
+
+    def forward(self, tokens):
+        tokens = tokens.to(self.device)
+        return self.transformer(tokens, return_embeddings=True)
+
+    def encode(self, x):
+        return self(x)
+
+
+class BERTTokenizer(AbstractEncoder):
+    """Reference ``clip_encoder/modules.py:76-120``: the huggingface BERT tokenizer, padded to ``max_length``.
+    The reference downloads ``bert-base-uncased``; here ``version`` may be a LOCAL directory holding
+    ``vocab.txt`` (loaded with ``local_files_only=True``).  Without one the module constructs and
+    ``forward(text)`` raises."""
+
+    def __init__(self, device="cuda", vq_interface=True, max_length=77, version=None):
+        super().__init__()
+        self.tokenizer = None
+        if isinstance(version, str) and os.path.isdir(version) and os.path.exists(os.path.join(version, "vocab.txt")):
+            from transformers import BertTokenizerFast
+            self.tokenizer = BertTokenizerFast.from_pretrained(version, local_files_only=True)
+        self.device = device
+        self.vq_interface = vq_interface
+        self.max_length = max_length
+
+    def forward(self, text):
+        if self.tokenizer is None:
+            raise RuntimeError("sd_amd.BERTTokenizer: no local tokenizer (a directory with vocab.txt as `version`) — "
+                               "the hub download of the reference is unavailable offline; pass token ids")
+        batch_encoding = self.tokenizer(text, truncation=True, max_length=self.max_length, return_length=True,
+                                        return_overflowing_tokens=False, padding="max_length", return_tensors="pt")
+        return batch_encoding["input_ids"].to(self.device)
+
+    @torch.no_grad()
+    def encode(self, text):
+        tokens = self(text)
+        if not self.vq_interface:
+            return tokens
+        return None, None, [None, None, tokens]
+
+    def decode(self, text):
+        return text
+
+
+class BERTEmbedder(AbstractEncoder):
+    """Reference ``clip_encoder/modules.py:123-165``: the BERT tokenizer followed by transformer encoder layers
+    (LDM text-to-image: ``n_embed=1280, n_layer=32`` → a 77 x 1280 context).  A tensor argument is always taken
+    as token ids; text goes through the tokenizer (``tokenizer_version``: its local directory)."""
+
+    def __init__(self, n_embed, n_layer, vocab_size=30522, max_seq_len=77, device="cuda", use_tokenizer=True,
+                 embedding_dropout=0.0, tokenizer_version=None):
+        super().__init__()
+        from .x_transformer import Encoder, TransformerWrapper
+        self.use_tknz_fn = use_tokenizer
+        if self.use_tknz_fn:
+            self.tknz_fn = BERTTokenizer(device=device, vq_interface=False, max_length=max_seq_len,
+                                         version=tokenizer_version)
+        self.device = device
+        self.transformer = TransformerWrapper(num_tokens=vocab_size, max_seq_len=max_seq_len,
+                                              attn_layers=Encoder(dim=n_embed, depth=n_layer),
+                                              emb_dropout=embedding_dropout)
+
+    def forward(self, text):
+        if torch.is_tensor(text):
+            tokens = text
+        elif self.use_tknz_fn:
+            tokens = self.tknz_fn(text)
+        else:
+            raise TypeError("sd_amd.BERTEmbedder: use_tokenizer=False takes token ids (an integer tensor)")
+        return self.transformer(tokens, return_embeddings=True)
+
+    def encode(self, text):
+        return self(text)
+
+
+class SpatialRescaler(nn.Module):
+    """Reference ``clip_encoder/modules.py:168-209``: ``n_stages`` x ``F.interpolate(x, scale_factor=multiplier,
+    mode=method)``, then an optional 1x1 ``channel_mapper``.  fp32 NCHW in, fp32 NCHW out (what ``c_concat``
+    takes): one ``sdk_resize2d`` launch per stage; the mapper runs as the library's 1x1 conv on the fp16 NHWC
+    pack of the resized image and writes fp32 NCHW."""
+
+    def __init__(self, n_stages=1, method="bilinear", multiplier=0.5, in_channels=3, out_channels=None, bias=False):
+        super().__init__()
+        self.n_stages = n_stages
+        assert self.n_stages >= 0
+        assert method in ["nearest", "linear", "bilinear", "trilinear", "bicubic", "area"]
+        self.method = method
+        self.multiplier = multiplier
+        self.remap_output = out_channels is not None
+        if self.remap_output:
+            self.channel_mapper = nn.Conv2d(in_channels, out_channels, 1, bias=bias)
+        self._pc, self._pc_key = None, None
+
+    @torch.no_grad()
+    def forward(self, x):
+        if not torch.is_tensor(x) or x.dim() != 4:
+            raise ValueError("sd_amd.SpatialRescaler: expected an NCHW tensor")
+        if self.n_stages > 0 and self.method in ("linear", "trilinear"):
+            # torch itself: "Got 4D input, but linear mode needs 3D input" / trilinear 5D
+            raise NotImplementedError(f"sd_amd.SpatialRescaler: method={self.method!r} does not take a 4-D input "
+                                      "(torch's F.interpolate raises for it as well)")
+        if not x.is_cuda:
+            raise TypeError("sd_amd.SpatialRescaler: HIP path only — move the image to the GPU")
+        for _ in range(self.n_stages):
+            x = ops.resize2d(x, self.multiplier, self.method)
+        if self.remap_output:
+            m = self.channel_mapper
+            if x.dim() != 4 or x.shape[1] != m.in_channels:
+                raise ValueError(f"sd_amd.SpatialRescaler: channel_mapper takes {m.in_channels} channels, got "
+                                 f"{tuple(x.shape)}")
+            key = (x.device, m.weight._version, None if m.bias is None else m.bias._version, m.weight.data_ptr())
+            if self._pc_key != key:
+                self._c_pad = (m.in_channels + 7) // 8 * 8
+                self._pc = ops.PackedConv([(m.weight, self._c_pad)], m.bias, device=x.device)
+                self._pc_key = key
+            x = ops.conv2d(self._pc, ops.nchw_to_nhwc(x.float(), self._c_pad), out_mode=ops.OUT_NCHW_F32)
+        return x
+
+    def encode(self, x):
+        return self(x)
 
 
 class _Embeddings(nn.Module):

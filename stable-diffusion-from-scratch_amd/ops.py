@@ -919,6 +919,70 @@ def embedding_add(emb, table, ids):
     return out
 
 
+def embedding_rows(ids, table):
+    """``table[ids].half()`` — the ClassEmbedder row gather (``sdk_embedding_rows``).  ids int64 ``[n]``, table
+    fp32 ``[rows, dim]`` on the device → fp16 ``[n, dim]``; an id outside ``[0, rows)`` raises ValueError (checked
+    on the host before the launch: the kernel reads the table by the ids it is given)."""
+    _need_cuda(ids, "embedding_rows ids", torch.int64)
+    _need_cuda(table, "embedding_rows table", torch.float32)
+    if ids.dim() != 1 or ids.numel() < 1 or table.dim() != 2 or table.shape[1] < 1:
+        raise ValueError(f"sd_amd.embedding_rows: ids {tuple(ids.shape)} (want [n >= 1]), table {tuple(table.shape)} "
+                         "(want [rows, dim >= 1])")
+    if ids.device != table.device:
+        raise ValueError("sd_amd.embedding_rows: ids and table on different devices")
+    lo, hi = int(ids.min()), int(ids.max())
+    if lo < 0 or hi >= table.shape[0]:
+        raise ValueError(f"sd_amd.embedding_rows: id outside [0, {table.shape[0]}) (min {lo}, max {hi})")
+    ids, table = ids.contiguous(), table.contiguous()
+    n, dim = ids.shape[0], table.shape[1]
+    out = torch.empty(n, dim, dtype=torch.float16, device=table.device)
+    check(lib().sdk_embedding_rows(_ptr(ids), _ptr(table), _ptr(out), n, dim, _stream()), "embedding_rows")
+    return out
+
+
+RESIZE_MODES = {"nearest": _lib.RESIZE_NEAREST, "bilinear": _lib.RESIZE_BILINEAR, "bicubic": _lib.RESIZE_BICUBIC,
+                "area": _lib.RESIZE_AREA}
+
+
+def resize2d(x, scale_factor, mode="bilinear", out=None):
+    """``F.interpolate(x, scale_factor=scale_factor, mode=mode)`` with torch's defaults (align_corners=False, no
+    antialias, the given factor used for the coordinates) on NCHW fp32 (``sdk_resize2d``): ``[B, C, H, W]`` →
+    ``[B, C, floor(H * s), floor(W * s)]``.  ``scale_factor``: a number or an (h, w) pair; ``mode``: nearest /
+    bilinear / bicubic / area."""
+    _need_cuda(x, "resize2d", torch.float32)
+    if x.dim() != 4:
+        raise ValueError(f"sd_amd.resize2d: expected NCHW, got {tuple(x.shape)}")
+    if mode not in RESIZE_MODES:
+        raise ValueError(f"sd_amd.resize2d: mode {mode!r} not in {sorted(RESIZE_MODES)}")
+    sh, sw = (scale_factor if isinstance(scale_factor, (tuple, list)) else (scale_factor, scale_factor))
+    sh, sw = float(sh), float(sw)
+    if not (sh > 0 and sw > 0 and math.isfinite(sh) and math.isfinite(sw)):
+        raise ValueError(f"sd_amd.resize2d: scale_factor {scale_factor!r} must be positive and finite")
+    B, Cc, H, W = x.shape
+    Ho, Wo = math.floor(H * sh), math.floor(W * sw)
+    if min(B, Cc, H, W, Ho, Wo) < 1:
+        raise ValueError(f"sd_amd.resize2d: empty input or output ({tuple(x.shape)} -> {Ho} x {Wo})")
+    if B * Cc >= 2 ** 31 or max(H, W, Ho, Wo) >= 2 ** 31:
+        raise ValueError("sd_amd.resize2d: sizes exceed int32")
+    x = x.contiguous()
+    if out is None:
+        out = torch.empty(B, Cc, Ho, Wo, dtype=torch.float32, device=x.device)
+    else:
+        _need_cuda(out, "resize2d out", torch.float32)
+        if tuple(out.shape) != (B, Cc, Ho, Wo) or not out.is_contiguous() or out.device != x.device:
+            raise ValueError(f"sd_amd.resize2d: out must be contiguous {(B, Cc, Ho, Wo)} on the input's device")
+    a = _lib.Resize2dArgs()
+    a.x, a.y = x.data_ptr(), out.data_ptr()
+    a.planes, a.h, a.w, a.out_h, a.out_w = B * Cc, H, W, Ho, Wo
+    a.mode, a.scale_h, a.scale_w = RESIZE_MODES[mode], sh, sw
+    if PROFILER.active:
+        PROFILER.begin("resize2d", None, nbytes=4 * (x.numel() + out.numel()))
+    check(lib().sdk_resize2d(C.byref(a), _stream()), "resize2d")
+    if PROFILER.active:
+        PROFILER.end()
+    return out
+
+
 def layer_norm(x2d, gamma, beta, eps=1e-5, out=None):
     _need_cuda(x2d, "layer_norm")
     M, Cc = x2d.shape
