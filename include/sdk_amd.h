@@ -206,6 +206,26 @@ int sdk_group_norm_finalize(const sdk_group_norm_args* a, const float* part0, in
 int sdk_group_norm_apply_ex(const sdk_group_norm_args* a, int32_t silu, const float* post_bias, int32_t pb_ld,
                             const void* residual, int32_t res_ld, void* y, int32_t ld_y, sdk_stream_t stream);
 
+/* The launches a GroupNorm call takes, decided on the host exactly as the entry points above decide them
+ * (they route through the same planner): no device is touched and no pointer is followed beyond `a`, so
+ * tests and tools can ask which form runs.  want_stats / want_apply: the affine is computed / the transform
+ * is written (sdk_group_norm: both; sdk_group_norm_affine / _finalize: statistics only; sdk_group_norm_apply /
+ * _apply_padded: apply only, a->scale / a->shift given).  h * w == a->hw, pad in [0, 4] (pad 0 is applied as the
+ * image 1 x hw).  nch0 / nch1 != 0: the producers' partials are given with that many chunks.
+ * allow_single_launch = 0 is sdk_group_norm_film, which folds FiLM into the affine between the two passes.
+ * Validates as those entry points do (non-zero = they reject the call). */
+enum { SDK_GN_STATS_GIVEN = 0,   /* a->scale / a->shift already hold the affine */
+       SDK_GN_STATS_SLICE,       /* gn_stats_fused_kernel: one launch, no workspace */
+       SDK_GN_STATS_CHUNKED,     /* gn_partial + gn_finalize: two launches, workspace */
+       SDK_GN_STATS_PARTS };     /* merged from the producing convs' partials */
+enum { SDK_GN_APPLY_NONE = 0,    /* statistics only */
+       SDK_GN_APPLY_IN_STATS,    /* same launch as the statistics (fused / from-partials single launch) */
+       SDK_GN_APPLY_FLAT, SDK_GN_APPLY_ROW, SDK_GN_APPLY_STRIDE };
+typedef struct { int32_t stats, apply, launches; int64_t workspace_bytes; } sdk_group_norm_plan_info;
+int sdk_group_norm_plan(const sdk_group_norm_args* a, int32_t want_stats, int32_t want_apply, int32_t h, int32_t w,
+                        int32_t pad, int32_t nch0, int32_t nch1, int32_t allow_single_launch,
+                        sdk_group_norm_plan_info* info);
+
 /* ---------------------------------------------------------------- device calibration probes
  * Not on the sampling path: measure, on the box the bench runs on, the dense fp16 MFMA rate held
  * under load (back-to-back v_mfma_f32_16x16x32_f16 (m16 = 1) or 32x32x16 on random register

@@ -44,6 +44,10 @@ class GroupNormArgs(C.Structure):
                 ("scale", vp), ("shift", vp), ("workspace", vp), ("workspace_bytes", i64)]
 
 
+class GroupNormPlanInfo(C.Structure):
+    _fields_ = [("stats", i32), ("apply", i32), ("launches", i32), ("workspace_bytes", i64)]
+
+
 class AttentionArgs(C.Structure):
     _fields_ = [("q", vp), ("k", vp), ("v", vp), ("o", vp), ("q_ld", i32), ("k_ld", i32), ("v_ld", i32),
                 ("o_ld", i32), ("batch", i32), ("heads", i32), ("nq", i32), ("nk", i32), ("head_dim", i32),
@@ -109,8 +113,10 @@ RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_BICUBIC, RESIZE_AREA = range(4)
 ACT_NONE, ACT_QUICK_GELU = 0, 1
 ATTN_AUTO, ATTN_NW4, ATTN_NW8, ATTN_NW8_STAG, ATTN_QB2 = range(5)
 RESAMPLE_AVGPOOL2, RESAMPLE_NEAREST2 = 0, 1
+GN_STATS = ("given", "slice", "chunked", "parts")              # SDK_GN_STATS_*
+GN_APPLY = ("none", "in_stats", "flat", "row", "stride")       # SDK_GN_APPLY_*
 
-EXPORTS = ["sdk_conv2d_plan", "sdk_conv2d", "sdk_group_norm_workspace", "sdk_group_norm_affine", "sdk_group_norm_apply", "sdk_group_norm_apply_padded", "sdk_group_norm_apply_ex", "sdk_group_norm", "sdk_group_norm_finalize", "sdk_layer_norm",
+EXPORTS = ["sdk_conv2d_plan", "sdk_conv2d", "sdk_group_norm_workspace", "sdk_group_norm_affine", "sdk_group_norm_apply", "sdk_group_norm_apply_padded", "sdk_group_norm_apply_ex", "sdk_group_norm", "sdk_group_norm_finalize", "sdk_group_norm_plan", "sdk_layer_norm",
            "sdk_attention", "sdk_attention_form", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_posterior_step", "sdk_masked_q_sample", "sdk_concat_nchw_to_nhwc", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
            "sdk_diag_gaussian_sample", "sdk_stochastic_encode", "sdk_token_embedding", "sdk_extract_patches",
            "sdk_fold_patches", "sdk_vq_code_norms", "sdk_vq_nearest_splits", "sdk_vq_nearest", "sdk_vq_lookup", "sdk_vq_remap",
@@ -144,6 +150,8 @@ def lib():
     L.sdk_group_norm_finalize.argtypes = [C.POINTER(GroupNormArgs), vp, i32, vp, i32, vp]
     L.sdk_group_norm_film.argtypes = [C.POINTER(GroupNormArgs), vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp,
                                       i32, vp]
+    L.sdk_group_norm_plan.argtypes = [C.POINTER(GroupNormArgs), i32, i32, i32, i32, i32, i32, i32, i32,
+                                      C.POINTER(GroupNormPlanInfo)]
     L.sdk_group_norm_resample.argtypes = [C.POINTER(GroupNormArgs), i32, i32, i32, i32, i32, vp, vp, vp]
     L.sdk_embedding_add.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     L.sdk_embedding_rows.argtypes = [vp, vp, vp, i32, i32, vp]

@@ -9,10 +9,7 @@
 // for offset activations); pass 2 merges chunks in double per channel and
 // channels into groups with Chan's parallel-variance formula.
 #include <algorithm>
-#include <cstdlib>
-
-#include <map>
-#include <mutex>
+#include <string>
 
 #include "common.h"
 
@@ -45,6 +42,29 @@ __device__ __forceinline__ h8 load_px(const half_t* s0, const half_t* s1, int c_
                                       size_t pix, int c) {
   if (c < c_split) return *reinterpret_cast<const h8*>(s0 + pix * ld0 + c);
   return *reinterpret_cast<const h8*>(s1 + pix * ld1 + (c - c_split));
+}
+
+// The GroupNorm transform of every apply form below, written once: the routes give equal bits because they all
+// go through here.  Eight scale or shift values from global memory or LDS as two 16-B loads:
+__device__ __forceinline__ void gn_load8(const float* p, float o[8]) {
+  const f4* q = reinterpret_cast<const f4*>(p);
+  const f4 a = q[0], b = q[1];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { o[j] = a[j]; o[4 + j] = b[j]; }
+}
+
+// silu?(x*sc + sh) in fp32 (the avg-pool resample sums four of these before it rounds)
+__device__ __forceinline__ float gn_act(float x, float sc, float sh, int silu) {
+  float t = x * sc + sh;
+  if (silu) t = t * __builtin_amdgcn_rcpf(1.0f + __expf(-t));
+  return t;
+}
+
+__device__ __forceinline__ h8 gn_act8(h8 v, const float sc[8], const float sh[8], int silu) {
+  h8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = (half_t)gn_act((float)v[j], sc[j], sh[j], silu);
+  return o;
 }
 
 // grid (nchunks, batch); writes partial[b][chunk][c] = (S1, S2) of (x - pivot_c)
@@ -304,17 +324,36 @@ __global__ void __launch_bounds__(GNF_T) gn_stats_fused_kernel(const half_t* s0,
         const int rr = r + u * rp;
         if (rr >= npix) continue;
         h8 o = {};
-        if (in[u]) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            float t = (float)x[u][j] * sa[j] + sh[j];
-            if (silu) t = t * __builtin_amdgcn_rcpf(1.0f + __expf(-t));
-            o[j] = (half_t)t;
-          }
-        }
+        if (in[u]) o = gn_act8(x[u], sa, sh, silu);
         *reinterpret_cast<h8*>(yb + (size_t)rr * ldy) = o;
       }
     }
+  }
+}
+
+// One wave Chan-merges the cg channels of a group (cm = per-channel mean, cq = per-channel M2, each over n pixels)
+// into the group's (mean, rstd) and hands every channel's affine to put(ci, c, scale, shift), c = c0 + ci.
+template <class Put>
+__device__ __forceinline__ void gn_merge_group(const double* cm, const double* cq, int cg, double n, float eps, int c0,
+                                               const float* gamma, const float* beta, int lane, Put put) {
+  double mean_sum = 0.0;
+  for (int ci = lane; ci < cg; ci += 64) mean_sum += cm[ci];
+  mean_sum = wave_sum_d(mean_sum);
+  const double mg = mean_sum / cg;
+  double m2g = 0.0;
+  for (int ci = lane; ci < cg; ci += 64) {
+    const double dm = cm[ci] - mg;
+    m2g += cq[ci] + n * dm * dm;
+  }
+  m2g = wave_sum_d(m2g);
+  const double var = (m2g > 0 ? m2g : 0.0) / (n * cg);
+  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+  const float meanf = (float)mg;
+  for (int ci = lane; ci < cg; ci += 64) {
+    const int c = c0 + ci;
+    const float gm = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
+    const float sc = gm * rstd;
+    put(ci, c, sc, bt - meanf * sc);
   }
 }
 
@@ -369,37 +408,20 @@ __global__ void __launch_bounds__(256) gn_finalize_part_kernel(const float2* par
   }
   __syncthreads();
   if (wave != 0) return;
-  const double n = (double)hw;
-  double mean_sum = 0.0;
-  for (int ci = lane; ci < cg; ci += 64) mean_sum += cm[ci];
-  mean_sum = wave_sum_d(mean_sum);
-  const double mg = mean_sum / cg;
-  double m2g = 0.0;
-  for (int ci = lane; ci < cg; ci += 64) {
-    const double dm = cm[ci] - mg;
-    m2g += cq[ci] + n * dm * dm;
-  }
-  m2g = wave_sum_d(m2g);
-  const double var = (m2g > 0 ? m2g : 0.0) / (n * cg);
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float meanf = (float)mg;
-  for (int ci = lane; ci < cg; ci += 64) {
-    const int c = c0 + ci;
-    const float gm = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
-    const float sc = gm * rstd;
+  gn_merge_group(cm, cq, cg, (double)hw, eps, c0, gamma, beta, lane, [&](int, int c, float sc, float sh) {
     scale[(size_t)b * channels + c] = sc;
-    shift[(size_t)b * channels + c] = bt - meanf * sc;
-  }
+    shift[(size_t)b * channels + c] = sh;
+  });
 }
 
 // GroupNorm apply whose prologue merges the producers' partials itself (one launch instead of
 // gn_finalize_part + apply: at the 32x32 / 16x16 / 8x8 levels both are latency-floor launches).
 // grid (groups / gps channel slices, batch, row splits of the output image): a workgroup Chan-merges
 // its slice's channels over the partial chunks (double, chunk order), merges the slice's groups from
-// the channels exactly as gn_finalize_part_kernel does, keeps scale / shift in LDS and normalises
+// the channels with gn_finalize_part_kernel's gn_merge_group, keeps scale / shift in LDS and normalises
 // (+ SiLU) its rows of the (optionally zero-bordered) image for the slice's channels.  The partials
 // are read once per workgroup from L2 (nch x slice x 8 B), so the path is taken only for hw up to
-// SDK_GN_PART_FUSED_MAX_HW (default 256: the 16x16 / 8x8 levels, 7.6 vs 9.8 us per GroupNorm at 8x8;
+// GN_PARTS_SINGLE_MAX_HW (256: the 16x16 / 8x8 levels, 7.6 vs 9.8 us per GroupNorm at 8x8;
 // at 32x32 the per-workgroup prologue repeats over too many row splits: 16-17 vs 15.4 us, measured
 // same-box, UNet step 21.07 -> 21.01 ms at 256 and 21.10 at 1024).
 constexpr int GNP_MAXCS = 256, GNP_MAXCH = 16;   // slice channels, partial chunks per source
@@ -443,32 +465,16 @@ __global__ void __launch_bounds__(256) gn_apply_part_kernel(const float2* part0,
     cq[cc] = m2 + rows * dd;
   }
   __syncthreads();
-  for (int gi = wave; gi < gps; gi += 4) {
-    double ms = 0.0;
-    for (int ci = lane; ci < cg; ci += 64) ms += cm[gi * cg + ci];
-    ms = wave_sum_d(ms);
-    const double mg = ms / cg;
-    double m2g = 0.0;
-    for (int ci = lane; ci < cg; ci += 64) {
-      const double dm = cm[gi * cg + ci] - mg;
-      m2g += cq[gi * cg + ci] + (double)hw * dm * dm;
-    }
-    m2g = wave_sum_d(m2g);
-    const double var = (m2g > 0 ? m2g : 0.0) / ((double)hw * cg);
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float meanf = (float)mg;
-    for (int ci = lane; ci < cg; ci += 64) {
-      const int c = c0 + gi * cg + ci;
-      const float gm = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
-      const float sc = gm * rstd, sh = bt - meanf * sc;
-      sc_s[gi * cg + ci] = sc;
-      sh_s[gi * cg + ci] = sh;
-      if (scale && blockIdx.z == 0) {
-        scale[(size_t)b * channels + c] = sc;
-        shift[(size_t)b * channels + c] = sh;
-      }
-    }
-  }
+  for (int gi = wave; gi < gps; gi += 4)
+    gn_merge_group(cm + gi * cg, cq + gi * cg, cg, (double)hw, eps, c0 + gi * cg, gamma, beta, lane,
+                   [&](int ci, int c, float sc, float sh) {
+                     sc_s[gi * cg + ci] = sc;
+                     sh_s[gi * cg + ci] = sh;
+                     if (scale && blockIdx.z == 0) {
+                       scale[(size_t)b * channels + c] = sc;
+                       shift[(size_t)b * channels + c] = sh;
+                     }
+                   });
   __syncthreads();
   const int hp = h + 2 * pad, wp = w + 2 * pad, npix = hp * wp, v8 = cs / 8;
   const int r0 = blockIdx.z * rows_per, r1 = min(npix, r0 + rows_per);
@@ -491,12 +497,10 @@ __global__ void __launch_bounds__(256) gn_apply_part_kernel(const float2* part0,
       if (e >= total) break;
       h8 o = {};
       if (in[u]) {
+        float sc[8], sh[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float x = (float)v[u][j] * sc_s[cv + j] + sh_s[cv + j];
-          if (silu) x = x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-          o[j] = (half_t)x;
-        }
+        for (int j = 0; j < 8; ++j) { sc[j] = sc_s[cv + j]; sh[j] = sh_s[cv + j]; }
+        o = gn_act8(v[u], sc, sh, silu);
       }
       *reinterpret_cast<h8*>(yb + (size_t)rr * ldy + cv) = o;
     }
@@ -526,63 +530,39 @@ int gn_fused_gps(int channels, int groups) {
 // 16-B loads/stores, reads the (optional) 2-source concat and writes it contiguous.
 // Applying the per-tap prologue inside a 3x3 implicit GEMM would repeat this
 // VALU work 9x per element; one streaming pass is HBM-bound instead.
-__global__ void __launch_bounds__(256) gn_apply_kernel(const half_t* s0, const half_t* s1, int c_split, int ld0,
-                                                       int ld1, int hw, int channels, const float* scale,
-                                                       const float* shift, int silu, half_t* y, int ldy,
-                                                       int64_t nvec) {
-  const int c8 = channels / 8;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < nvec; e += stride) {
-    const int64_t pix = e / c8;
-    const int c = (int)(e - pix * c8) * 8;
-    const int b = (int)(pix / hw);
-    h8 v = load_px(s0, s1, c_split, ld0, ld1, (size_t)pix, c);
-    const f4* ps = reinterpret_cast<const f4*>(scale + (size_t)b * channels + c);
-    const f4* pt = reinterpret_cast<const f4*>(shift + (size_t)b * channels + c);
-    const f4 sa = ps[0], sb = ps[1], ta = pt[0], tb = pt[1];
-    const float sc[8] = {sa[0], sa[1], sa[2], sa[3], sb[0], sb[1], sb[2], sb[3]};
-    const float sh[8] = {ta[0], ta[1], ta[2], ta[3], tb[0], tb[1], tb[2], tb[3]};
-    h8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float x = (float)v[j] * sc[j] + sh[j];
-      if (silu) x = x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-      o[j] = (half_t)x;
-    }
-    *reinterpret_cast<h8*>(y + (size_t)pix * ldy + c) = o;
-  }
-}
-
-// The same transform written into a zero-bordered image [B][h+2p][w+2p][ldy]: the 3x3 conv that
-// consumes it runs with pad 0, every tap in range — no per-tap masks in its A gather.
-__global__ void __launch_bounds__(256) gn_apply_pad_kernel(const half_t* s0, const half_t* s1, int c_split, int ld0,
-                                                           int ld1, int h, int w, int pad, int channels,
-                                                           const float* scale, const float* shift, int silu,
-                                                           half_t* y, int ldy, int64_t nvec) {
+// PAD: written into a zero-bordered image [B][h+2p][w+2p][ldy]: the 3x3 conv that consumes it runs with pad 0,
+// every tap in range — no per-tap masks in its A gather.  Without PAD the output pixel is the input pixel (hw
+// pixels per image; h / w / pad unused, no border arithmetic).  Grid-stride over the 8-channel vectors.
+template <bool PAD>
+__global__ void __launch_bounds__(256) gn_apply_stride_kernel(const half_t* s0, const half_t* s1, int c_split,
+                                                              int ld0, int ld1, int hw, int h, int w, int pad,
+                                                              int channels, const float* scale, const float* shift,
+                                                              int silu, half_t* y, int ldy, int64_t nvec) {
   const int c8 = channels / 8;
   const int hp = h + 2 * pad, wp = w + 2 * pad;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < nvec; e += stride) {
-    const int64_t ppix = e / c8;
+    const int64_t ppix = e / c8;   // output pixel
     const int c = (int)(e - ppix * c8) * 8;
-    const int b = (int)(ppix / ((int64_t)hp * wp));
-    const int r = (int)(ppix - (int64_t)b * hp * wp);
-    const int iy = r / wp - pad, ix = r % wp - pad;
+    int b;
+    size_t pix = (size_t)ppix;     // input pixel
+    bool in = true;
+    if constexpr (PAD) {
+      b = (int)(ppix / ((int64_t)hp * wp));
+      const int r = (int)(ppix - (int64_t)b * hp * wp);
+      const int iy = r / wp - pad, ix = r % wp - pad;
+      in = (unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w;
+      pix = ((size_t)b * h + iy) * w + ix;
+    } else {
+      b = (int)(ppix / hw);
+    }
     h8 o = {};
-    if ((unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w) {
-      const size_t pix = ((size_t)b * h + iy) * w + ix;
+    if (in) {
       const h8 v = load_px(s0, s1, c_split, ld0, ld1, pix, c);
-      const f4* ps = reinterpret_cast<const f4*>(scale + (size_t)b * channels + c);
-      const f4* pt = reinterpret_cast<const f4*>(shift + (size_t)b * channels + c);
-      const f4 sa = ps[0], sb = ps[1], ta = pt[0], tb = pt[1];
-      const float sc[8] = {sa[0], sa[1], sa[2], sa[3], sb[0], sb[1], sb[2], sb[3]};
-      const float sh[8] = {ta[0], ta[1], ta[2], ta[3], tb[0], tb[1], tb[2], tb[3]};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float x = (float)v[j] * sc[j] + sh[j];
-        if (silu) x = x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-        o[j] = (half_t)x;
-      }
+      float sc[8], sh[8];
+      gn_load8(scale + (size_t)b * channels + c, sc);
+      gn_load8(shift + (size_t)b * channels + c, sh);
+      o = gn_act8(v, sc, sh, silu);
     }
     *reinterpret_cast<h8*>(y + (size_t)ppix * ldy + c) = o;
   }
@@ -622,17 +602,10 @@ __global__ void __launch_bounds__(256) gn_apply_flat_kernel(const half_t* s0, co
     if (e0 + 256u * u >= nvec) break;
     h8 o = {};
     if (in[u]) {
-      const f4* ps = reinterpret_cast<const f4*>(scale + (size_t)bb[u] * channels + cc[u]);
-      const f4* pt = reinterpret_cast<const f4*>(shift + (size_t)bb[u] * channels + cc[u]);
-      const f4 sa = ps[0], sb = ps[1], ta = pt[0], tb = pt[1];
-      const float sc[8] = {sa[0], sa[1], sa[2], sa[3], sb[0], sb[1], sb[2], sb[3]};
-      const float sh[8] = {ta[0], ta[1], ta[2], ta[3], tb[0], tb[1], tb[2], tb[3]};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float x = (float)v[u][j] * sc[j] + sh[j];
-        if (silu) x = x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-        o[j] = (half_t)x;
-      }
+      float sc[8], sh[8];
+      gn_load8(scale + (size_t)bb[u] * channels + cc[u], sc);
+      gn_load8(shift + (size_t)bb[u] * channels + cc[u], sh);
+      o = gn_act8(v[u], sc, sh, silu);
     }
     *reinterpret_cast<h8*>(y + (size_t)ppix[u] * ldy + cc[u]) = o;
   }
@@ -677,17 +650,10 @@ __global__ void __launch_bounds__(256) gn_apply_pad_row_kernel(const half_t* s0,
       if (i0 + 256 * u >= n) break;
       h8 o = {};
       if (in[u]) {
-        const f4* ps = reinterpret_cast<const f4*>(gst + cc[u]);
-        const f4* pt = reinterpret_cast<const f4*>(gst + channels + cc[u]);
-        const f4 sa = ps[0], sb = ps[1], ta = pt[0], tb = pt[1];
-        const float sc[8] = {sa[0], sa[1], sa[2], sa[3], sb[0], sb[1], sb[2], sb[3]};
-        const float sh[8] = {ta[0], ta[1], ta[2], ta[3], tb[0], tb[1], tb[2], tb[3]};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float x = (float)v[u][j] * sc[j] + sh[j];
-          if (silu) x = x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-          o[j] = (half_t)x;
-        }
+        float sc[8], sh[8];
+        gn_load8(gst + cc[u], sc);
+        gn_load8(gst + channels + cc[u], sh);
+        o = gn_act8(v[u], sc, sh, silu);
       }
       *reinterpret_cast<h8*>(yrow + (size_t)px[u] * ldy + cc[u]) = o;
     }
@@ -816,20 +782,14 @@ __global__ void __launch_bounds__(256) gn_resample_kernel(const half_t* s0, cons
       h8 oa = {}, orw = {};
       if (in[u]) {
         if (act) {
-          const f4* ps = reinterpret_cast<const f4*>(gst + cc[u]);
-          const f4* pt = reinterpret_cast<const f4*>(gst + channels + cc[u]);
-          const f4 sa = ps[0], sb = ps[1], ta = pt[0], tb = pt[1];
-          const float sc[8] = {sa[0], sa[1], sa[2], sa[3], sb[0], sb[1], sb[2], sb[3]};
-          const float sh[8] = {ta[0], ta[1], ta[2], ta[3], tb[0], tb[1], tb[2], tb[3]};
+          float sc[8], sh[8];
+          gn_load8(gst + cc[u], sc);
+          gn_load8(gst + channels + cc[u], sh);
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
-            float acc = 0.f;
+            float acc = 0.f;   // 0 + x also for the single nearest-x2 value: a -0 result is written as +0
 #pragma unroll
-            for (int k = 0; k < NL; ++k) {
-              float x = (float)v[u][k][j] * sc[j] + sh[j];
-              if (silu) x = x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-              acc += x;
-            }
+            for (int k = 0; k < NL; ++k) acc += gn_act((float)v[u][k][j], sc[j], sh[j], silu);
             oa[j] = (half_t)(DOWN ? acc * 0.25f : acc);
           }
         }
@@ -902,8 +862,7 @@ __global__ void __launch_bounds__(256) gn_apply_ex_kernel(const half_t* s0, cons
     h8 o;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      float x = (float)v[j] * scale[(size_t)b * channels + c + j] + shift[(size_t)b * channels + c + j];
-      if (silu) x = x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
+      float x = gn_act((float)v[j], scale[(size_t)b * channels + c + j], shift[(size_t)b * channels + c + j], silu);
       if (pb) x += pb[(size_t)b * pb_ld + c + j];
       if (res) x += (float)r[j];
       o[j] = (half_t)x;
@@ -1012,120 +971,261 @@ __global__ void __launch_bounds__(256) layer_norm_quad_kernel(const half_t* x, h
 
 using namespace sdk;
 
-// largest pixels-per-image for the single-launch statistics (SDK_GN_FUSED_MAX_HW, read at load;
-// measured crossover on MI355X: tools/bench_norm.py)
-static const int g_gn_fused_max_hw = [] {
-  const char* e = getenv("SDK_GN_FUSED_MAX_HW");
-  return e ? atoi(e) : 1024;
-}();
-
 extern "C" int64_t sdk_group_norm_workspace(int32_t batch, int32_t hw, int32_t channels) {
   if (batch <= 0 || hw <= 0 || channels <= 0) return 0;
   GnGeom g = gn_geom(batch, hw, channels);
   return (int64_t)batch * g.nchunks * channels * (int64_t)sizeof(float2);
 }
 
-extern "C" int sdk_group_norm_affine(const sdk_group_norm_args* a, sdk_stream_t stream) {
-  if (!a || !a->src0 || !a->scale || !a->shift) return fail(SDK_EINVAL, "group_norm: null pointer");
-  if (a->channels % 8 || a->channels % a->groups || a->c_split % 8 || a->c_split <= 0 || a->c_split > a->channels)
-    return fail(SDK_EINVAL, "group_norm: channels/c_split must be multiples of 8, channels % groups == 0");
-  if (a->channels / a->groups > 256) return fail(SDK_EINVAL, "group_norm: > 256 channels per group");
-  if (a->c_split < a->channels && !a->src1) return fail(SDK_EINVAL, "group_norm: concat without src1");
-  if (a->ld0 % 8 || (a->c_split < a->channels && a->ld1 % 8)) return fail(SDK_EINVAL, "group_norm: ld % 8");
-  if (a->channels / 8 > 512) return fail(SDK_EINVAL, "group_norm: channels > 4096");
-  hipStream_t s = (hipStream_t)stream;
-  const int gps = gn_fused_gps(a->channels, a->groups);
-  if (gps > 0 && a->hw <= g_gn_fused_max_hw) {
-    hipLaunchKernelGGL(gn_stats_fused_kernel<false>, dim3(a->groups / gps, a->batch), dim3(GNF_T), 0, s,
-                       (const half_t*)a->src0, (const half_t*)a->src1, a->c_split, a->ld0, a->ld1, a->hw, a->channels,
-                       a->channels / a->groups, gps, a->eps, a->gamma, a->beta, a->scale, a->shift, 0, nullptr, 0,
-                       0, 0, 0);
-    return check_launch("gn_stats_fused");
+// ---------------------------------------------------------------- GroupNorm host plan
+// Every GroupNorm entry point fills a GnReq and calls gn_run: gn_plan validates and routes on the host (no device,
+// no pointer followed beyond the args), gn_launch_stats / gn_launch_apply switch on its result.  No launch
+// condition lives anywhere else; sdk_group_norm_plan reports the same plan to tests and tools.
+//
+// largest pixels-per-image for the single-launch statistics (measured crossover on MI355X: tools/bench_norm.py,
+// profiles/r2_gn_fused_stats_ab.txt)
+constexpr int GN_SLICE_MAX_HW = 1024;
+// ... and for statistics + apply in that one launch (the 8x8 level)
+constexpr int GN_SLICE_APPLY_MAX_HW = 64;
+// largest image (h*w) whose GroupNorm-from-partials runs as one gn_apply_part_kernel launch (see that kernel)
+constexpr int GN_PARTS_SINGLE_MAX_HW = 256;
+// gn_apply_flat_kernel below this many pixels per image (profiles/r5_gn_apply_flat_ab.txt); from it on the row form
+// where it measured faster (padded, the VAE decoder's >= 128x128 images: 206.6 -> 182.5 us at 128x128x512,
+// 696.6 -> 677.8 at 512x512x128; the grid-stride form 64x64x640 56.6 vs 58.9 us, 16x16 17.4 vs 19.4), else the
+// grid-stride form
+constexpr int GN_FLAT_BELOW_HW = 128 * 128;
+
+struct GnReq {
+  const char* who;                 // the entry point, for messages
+  const sdk_group_norm_args* a;
+  bool stats, apply;               // what to launch: the affine into a->scale / a->shift, the transform into y
+  bool single;                     // statistics + apply may share one launch (the affine then stays in LDS)
+  bool image;                      // h / w / pad given; else the image is 1 x hw, pad 0
+  int h, w, pad;
+  const float* part0; int nch0;    // the producers' partials (presence only: never read on the host)
+  const float* part1; int nch1;
+  void* y; int ld_y;
+};
+
+struct GnPlan {
+  sdk_group_norm_plan_info info;
+  int gps;                         // SLICE: groups per workgroup; PARTS with IN_STATS: groups per channel slice
+  GnGeom geom;                     // CHUNKED
+  int splits, rows_per;            // PARTS with IN_STATS: row splits of the output image
+  int h, w, pad;                   // the image the apply pass writes (pad 0 is planned as 1 x hw)
+  int64_t nvec;                    // its 8-channel vectors
+  unsigned blocks;                 // FLAT / STRIDE grid
+  unsigned m_c8, m_img, m_wp;      // FLAT multiply-shift reciprocals
+  unsigned divm;                   // ROW multiply-shift reciprocal
+};
+
+// the validation every entry point shares (what is required follows from what the request asks for)
+static int gn_check(const GnReq& r) {
+  const sdk_group_norm_args* a = r.a;
+  const std::string who = r.who;
+  if (!a || !a->src0 || (r.apply && !r.y)) return fail(SDK_EINVAL, who + ": null pointer");
+  if (a->channels % 8 || a->c_split % 8 || a->c_split <= 0 || a->c_split > a->channels)
+    return fail(SDK_EINVAL, who + ": channels/c_split must be multiples of 8");
+  if (r.apply && (r.ld_y % 8 || r.ld_y < a->channels)) return fail(SDK_EINVAL, who + ": ld_y % 8, ld_y >= channels");
+  const bool concat = a->c_split < a->channels, parts = r.part0 && (!concat || r.part1);
+  if (r.stats) {
+    if (a->groups <= 0 || a->channels % a->groups) return fail(SDK_EINVAL, who + ": channels % groups == 0");
+    if (a->channels / a->groups > 256) return fail(SDK_EINVAL, who + ": > 256 channels per group");
+    // (the apply-only entries, and FiLM on partials, accept source rows that are not multiples of 8)
+    if ((!parts || r.single) && (a->ld0 % 8 || (concat && a->ld1 % 8))) return fail(SDK_EINVAL, who + ": ld % 8");
+    if (parts && (r.nch0 <= 0 || a->hw % r.nch0 || (concat && (r.nch1 <= 0 || a->hw % r.nch1))))
+      return fail(SDK_EINVAL, who + ": partial chunks must divide hw");
   }
-  const int64_t need = sdk_group_norm_workspace(a->batch, a->hw, a->channels);
-  if (!a->workspace || a->workspace_bytes < need) return fail(SDK_EWORKSPACE, "group_norm: workspace too small");
-  GnGeom g = gn_geom(a->batch, a->hw, a->channels);
-  const size_t lds = g.ry > 1 ? (size_t)2 * g.ry * g.c8 * 8 * sizeof(float) : 0;
-  hipLaunchKernelGGL(gn_partial_kernel, dim3(g.nchunks, a->batch), dim3(256), lds, s, (const half_t*)a->src0,
-                     (const half_t*)a->src1, a->c_split, a->ld0, a->ld1, a->hw, a->channels, g,
-                     (float2*)a->workspace);
-  if (int e = check_launch("gn_partial")) return e;
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(a->groups, a->batch), dim3(256), 0, s, (const half_t*)a->src0,
-                     (const half_t*)a->src1, a->c_split, a->ld0, a->ld1, a->hw, a->channels, a->groups, g,
-                     (const float2*)a->workspace, a->eps, a->gamma, a->beta, a->scale, a->shift);
-  return check_launch("gn_finalize");
+  if (concat && !a->src1 && (r.apply || !parts)) return fail(SDK_EINVAL, who + ": concat without src1");
+  if (r.image && (r.h <= 0 || r.w <= 0 || (int64_t)r.h * r.w != a->hw || r.pad < 0 || r.pad > 4))
+    return fail(SDK_EINVAL, who + ": h*w must equal hw, pad in [0, 4]");
+  return SDK_OK;
 }
 
-// SDK_GN_APPLY_FLAT: 1 (default) = gn_apply_flat_kernel below 128x128 pixels, 2 = everywhere, 0 = the grid-stride /
-// row forms only (A/B)
-static const int g_gn_apply_flat = [] {
-  const char* e = getenv("SDK_GN_APPLY_FLAT");
-  return e ? atoi(e) : 1;
-}();
+static int gn_plan(const GnReq& r, GnPlan& p) {
+  p = GnPlan{};
+  if (int e = gn_check(r)) return e;
+  const sdk_group_norm_args* a = r.a;
+  sdk_group_norm_plan_info& f = p.info;
+  if (a->batch <= 0) return SDK_OK;   // nothing to do
+  const bool concat = a->c_split < a->channels, parts = r.part0 && (!concat || r.part1);
+  const int rh = r.image ? r.h : 1, rw = r.image ? r.w : a->hw, rpad = r.image ? r.pad : 0;
+  if (r.stats && parts) {
+    f.stats = SDK_GN_STATS_PARTS;
+    const int pgps = gn_part_gps(a->channels, a->groups);
+    if (r.apply && r.single && pgps > 0 && a->hw <= GN_PARTS_SINGLE_MAX_HW && r.nch0 <= GNP_MAXCH &&
+        (!concat || r.nch1 <= GNP_MAXCH)) {
+      f.apply = SDK_GN_APPLY_IN_STATS;
+      p.gps = pgps;
+      const int cs = pgps * (a->channels / a->groups), slices = a->groups / pgps;
+      const int npix = (rh + 2 * rpad) * (rw + 2 * rpad);
+      // ~8 vectors per thread (one round of loads in flight), at least ~512 workgroups when the image allows
+      int splits = std::max(1, (npix * (cs / 8) + 2047) / 2048);
+      const int want = (512 + slices * a->batch - 1) / (slices * a->batch);
+      splits = std::min(std::max(splits, want), std::max(1, npix / 16));
+      p.rows_per = (npix + splits - 1) / splits;
+      p.splits = (npix + p.rows_per - 1) / p.rows_per;
+    }
+  } else if (r.stats) {
+    p.gps = gn_fused_gps(a->channels, a->groups);
+    if (p.gps > 0 && a->hw <= GN_SLICE_MAX_HW) {
+      f.stats = SDK_GN_STATS_SLICE;
+      if (r.apply && r.single && a->hw <= GN_SLICE_APPLY_MAX_HW) f.apply = SDK_GN_APPLY_IN_STATS;
+    } else {
+      f.stats = SDK_GN_STATS_CHUNKED;
+      p.geom = gn_geom(a->batch, a->hw, a->channels);
+      f.workspace_bytes = sdk_group_norm_workspace(a->batch, a->hw, a->channels);
+    }
+    if (f.apply != SDK_GN_APPLY_IN_STATS && a->channels / 8 > 512)
+      return fail(SDK_EINVAL, std::string(r.who) + ": channels > 4096");
+  }
+  if (f.apply != SDK_GN_APPLY_IN_STATS && (!a->scale || !a->shift))
+    return fail(SDK_EINVAL, std::string(r.who) + ": scale/shift buffers needed");
+  if (r.apply && f.apply != SDK_GN_APPLY_IN_STATS) {
+    p.pad = rpad;
+    p.h = rpad ? rh : 1;
+    p.w = rpad ? rw : a->hw;
+    const int hp = p.h + 2 * p.pad, wp = p.w + 2 * p.pad;
+    const int64_t npix = (int64_t)hp * wp, c8 = a->channels / 8, hw = (int64_t)p.h * p.w;
+    p.nvec = (int64_t)a->batch * npix * c8;
+    // the one-pass form when its reciprocals are exact over every index it forms (tail lanes included)
+    const int64_t span = p.nvec + 256 * GNA_U;
+    if (p.nvec > 0 && hw < GN_FLAT_BELOW_HW && span < (1LL << 31) && npix < (1 << 30)) {
+      p.m_c8 = c8 > 1 ? pad_row_divm((int)span, (int)c8) : 0u;
+      p.m_img = npix > 1 ? pad_row_divm((int)(span / c8 + 1), (int)npix) : 0u;
+      p.m_wp = wp > 1 ? pad_row_divm((int)npix, wp) : 0u;
+    }
+    if (p.nvec <= 0) {
+      f.apply = SDK_GN_APPLY_NONE;
+    } else if (p.m_c8 && p.m_img && p.m_wp) {
+      f.apply = SDK_GN_APPLY_FLAT;
+      p.blocks = (unsigned)((p.nvec + 256 * GNA_U - 1) / (256 * GNA_U));
+    } else {
+      if (p.pad > 0 && hw >= GN_FLAT_BELOW_HW && wp * c8 < (1 << 24) && a->channels <= 4096 && hp <= 65535 &&
+          a->batch <= 65535)
+        p.divm = pad_row_divm((int)(wp * c8), (int)c8);
+      f.apply = p.divm ? SDK_GN_APPLY_ROW : SDK_GN_APPLY_STRIDE;
+      p.blocks = (unsigned)std::min<int64_t>((p.nvec + 255) / 256, 8192);
+    }
+  }
+  const int stats_launches[] = {0, 1, 2, 1};
+  f.launches = stats_launches[f.stats] + (f.apply >= SDK_GN_APPLY_FLAT ? 1 : 0);
+  return SDK_OK;
+}
 
-// the one-pass apply when its reciprocals are exact over every index it forms (tail lanes included); 1 = launched
-static int gn_apply_flat(const sdk_group_norm_args* a, int silu, void* y, int ld_y, int h, int w, int pad,
-                         hipStream_t s) {
-  if (g_gn_apply_flat == 0 || (g_gn_apply_flat == 1 && (int64_t)h * w >= 128 * 128)) return 0;
-  const int64_t npix = (int64_t)(h + 2 * pad) * (w + 2 * pad), c8 = a->channels / 8;
-  const int64_t nvec = (int64_t)a->batch * npix * c8, span = nvec + 256 * GNA_U;
-  if (span >= (1LL << 31) || npix >= (1 << 30)) return 0;
-  const unsigned m_c8 = c8 > 1 ? pad_row_divm((int)span, (int)c8) : 0u;
-  const unsigned m_img = npix > 1 ? pad_row_divm((int)(span / c8 + 1), (int)npix) : 0u;
-  const unsigned m_wp = (w + 2 * pad) > 1 ? pad_row_divm((int)npix, w + 2 * pad) : 0u;
-  if (!m_c8 || !m_img || !m_wp) return 0;
-  const unsigned blocks = (unsigned)((nvec + 256 * GNA_U - 1) / (256 * GNA_U));
-  hipLaunchKernelGGL(gn_apply_flat_kernel, dim3(blocks), dim3(256), 0, s, (const half_t*)a->src0,
-                     (const half_t*)a->src1, a->c_split, a->ld0, a->ld1, h, w, pad, a->channels, a->scale, a->shift,
-                     silu, (half_t*)y, ld_y, (unsigned)nvec, m_c8, m_img, m_wp);
-  return 1;
+static int gn_launch_stats(const GnPlan& p, const GnReq& r, int silu, hipStream_t s) {
+  const sdk_group_norm_args* a = r.a;
+  const half_t *s0 = (const half_t*)a->src0, *s1 = (const half_t*)a->src1;
+  const bool in_stats = p.info.apply == SDK_GN_APPLY_IN_STATS;
+  switch (p.info.stats) {
+    case SDK_GN_STATS_SLICE:
+      hipLaunchKernelGGL(in_stats ? gn_stats_fused_kernel<true> : gn_stats_fused_kernel<false>,
+                         dim3(a->groups / p.gps, a->batch), dim3(GNF_T), 0, s, s0, s1, a->c_split, a->ld0, a->ld1,
+                         a->hw, a->channels, a->channels / a->groups, p.gps, a->eps, a->gamma, a->beta, a->scale,
+                         a->shift, silu, (half_t*)r.y, r.ld_y, r.h, r.w, r.pad);
+      return check_launch(in_stats ? "gn_fused_apply" : "gn_stats_fused");
+    case SDK_GN_STATS_CHUNKED: {
+      if (!a->workspace || a->workspace_bytes < p.info.workspace_bytes)
+        return fail(SDK_EWORKSPACE, std::string(r.who) + ": workspace too small");
+      const GnGeom& g = p.geom;
+      const size_t lds = g.ry > 1 ? (size_t)2 * g.ry * g.c8 * 8 * sizeof(float) : 0;
+      hipLaunchKernelGGL(gn_partial_kernel, dim3(g.nchunks, a->batch), dim3(256), lds, s, s0, s1, a->c_split, a->ld0,
+                         a->ld1, a->hw, a->channels, g, (float2*)a->workspace);
+      if (int e = check_launch("gn_partial")) return e;
+      hipLaunchKernelGGL(gn_finalize_kernel, dim3(a->groups, a->batch), dim3(256), 0, s, s0, s1, a->c_split, a->ld0,
+                         a->ld1, a->hw, a->channels, a->groups, g, (const float2*)a->workspace, a->eps, a->gamma,
+                         a->beta, a->scale, a->shift);
+      return check_launch("gn_finalize");
+    }
+    case SDK_GN_STATS_PARTS:
+      if (in_stats) {
+        hipLaunchKernelGGL(gn_apply_part_kernel, dim3(a->groups / p.gps, a->batch, p.splits), dim3(256), 0, s,
+                           (const float2*)r.part0, r.nch0, (const float2*)r.part1, r.nch1, s0, s1, a->c_split, a->ld0,
+                           a->ld1, r.h, r.w, r.pad, a->channels, a->channels / a->groups, p.gps, a->eps, a->gamma,
+                           a->beta, a->scale, a->shift, silu, (half_t*)r.y, r.ld_y, p.rows_per);
+        return check_launch("gn_apply_part");
+      }
+      hipLaunchKernelGGL(gn_finalize_part_kernel, dim3(a->groups, a->batch), dim3(256), 0, s, (const float2*)r.part0,
+                         r.nch0, (const float2*)r.part1, r.nch1, a->c_split, a->hw, a->channels, a->groups, a->eps,
+                         a->gamma, a->beta, a->scale, a->shift);
+      return check_launch("gn_finalize_part");
+    default:
+      return SDK_OK;   // SDK_GN_STATS_GIVEN
+  }
+}
+
+static int gn_launch_apply(const GnPlan& p, const GnReq& r, int silu, hipStream_t s) {
+  const sdk_group_norm_args* a = r.a;
+  const half_t *s0 = (const half_t*)a->src0, *s1 = (const half_t*)a->src1;
+  switch (p.info.apply) {
+    case SDK_GN_APPLY_FLAT:
+      hipLaunchKernelGGL(gn_apply_flat_kernel, dim3(p.blocks), dim3(256), 0, s, s0, s1, a->c_split, a->ld0, a->ld1, p.h,
+                         p.w, p.pad, a->channels, a->scale, a->shift, silu, (half_t*)r.y, r.ld_y, (unsigned)p.nvec,
+                         p.m_c8, p.m_img, p.m_wp);
+      return check_launch("gn_apply_flat");
+    case SDK_GN_APPLY_ROW:
+      hipLaunchKernelGGL(gn_apply_pad_row_kernel, dim3(p.h + 2 * p.pad, a->batch), dim3(256), (size_t)a->channels * 8, s,
+                         s0, s1, a->c_split, a->ld0, a->ld1, p.h, p.w, p.pad, a->channels, a->scale, a->shift, silu,
+                         (half_t*)r.y, r.ld_y, p.divm);
+      return check_launch("gn_apply_pad_row");
+    case SDK_GN_APPLY_STRIDE:
+      hipLaunchKernelGGL(p.pad ? gn_apply_stride_kernel<true> : gn_apply_stride_kernel<false>, dim3(p.blocks),
+                         dim3(256), 0, s, s0, s1, a->c_split, a->ld0, a->ld1, a->hw, p.h, p.w, p.pad, a->channels,
+                         a->scale, a->shift, silu, (half_t*)r.y, r.ld_y, p.nvec);
+      return check_launch("gn_apply_stride");
+    default:
+      return SDK_OK;   // SDK_GN_APPLY_NONE, or SDK_GN_APPLY_IN_STATS: the statistics launch wrote y
+  }
+}
+
+// FiLM ("scale-shift norm") folded into the affine between the statistics and the apply pass
+struct GnFilm {
+  const float* film;
+  int ld, off;
+};
+
+static int gn_run(const GnReq& r, int silu, sdk_stream_t stream, const GnFilm* film = nullptr) {
+  GnPlan p;
+  if (int e = gn_plan(r, p)) return e;
+  hipStream_t s = (hipStream_t)stream;
+  if (int e = gn_launch_stats(p, r, silu, s)) return e;
+  if (film && r.a->batch > 0) {
+    const int n = r.a->batch * r.a->channels;
+    hipLaunchKernelGGL(gn_film_fold_kernel, dim3((n + 255) / 256), dim3(256), 0, s, r.a->scale, r.a->shift, film->film,
+                       film->ld, film->off, r.a->channels, n);
+    if (int e = check_launch("gn_film_fold")) return e;
+  }
+  return gn_launch_apply(p, r, silu, s);
+}
+
+extern "C" int sdk_group_norm_plan(const sdk_group_norm_args* a, int32_t want_stats, int32_t want_apply, int32_t h,
+                                   int32_t w, int32_t pad, int32_t nch0, int32_t nch1, int32_t allow_single_launch,
+                                   sdk_group_norm_plan_info* info) {
+  if (!info) return fail(SDK_EINVAL, "group_norm_plan: null pointer");
+  static float present;   // stands for "this buffer is given"
+  GnReq r{"group_norm_plan", a, want_stats != 0, want_apply != 0, allow_single_launch != 0, true, h, w, pad,
+          nch0 ? &present : nullptr, nch0, nch1 ? &present : nullptr, nch1, &present, a ? a->channels : 0};
+  GnPlan p;
+  const int e = gn_plan(r, p);
+  *info = p.info;
+  return e;
+}
+
+extern "C" int sdk_group_norm_affine(const sdk_group_norm_args* a, sdk_stream_t stream) {
+  return gn_run(GnReq{"group_norm_affine", a, true, false, false, false, 0, 0, 0, nullptr, 0, nullptr, 0, nullptr, 0}, 0,
+                stream);
 }
 
 extern "C" int sdk_group_norm_apply(const sdk_group_norm_args* a, int32_t silu, void* y, int32_t ld_y,
                                     sdk_stream_t stream) {
-  if (!a || !a->src0 || !a->scale || !a->shift || !y) return fail(SDK_EINVAL, "group_norm_apply: null pointer");
-  if (a->channels % 8 || a->c_split % 8 || a->c_split <= 0 || a->c_split > a->channels || ld_y % 8 ||
-      ld_y < a->channels)
-    return fail(SDK_EINVAL, "group_norm_apply: channels/c_split/ld_y must be multiples of 8");
-  if (a->c_split < a->channels && !a->src1) return fail(SDK_EINVAL, "group_norm_apply: concat without src1");
-  const int64_t nvec = (int64_t)a->batch * a->hw * (a->channels / 8);
-  if (nvec <= 0) return SDK_OK;
-  if (a->hw < (1 << 30) && gn_apply_flat(a, silu, y, ld_y, 1, (int)a->hw, 0, (hipStream_t)stream))
-    return check_launch("gn_apply_flat");
-  const int blocks = (int)std::min<int64_t>((nvec + 255) / 256, 8192);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const half_t*)a->src0,
-                     (const half_t*)a->src1, a->c_split, a->ld0, a->ld1, a->hw, a->channels, a->scale, a->shift,
-                     silu, (half_t*)y, ld_y, nvec);
-  return check_launch("gn_apply");
+  return gn_run(GnReq{"group_norm_apply", a, false, true, false, false, 0, 0, 0, nullptr, 0, nullptr, 0, y, ld_y}, silu,
+                stream);
 }
 
 extern "C" int sdk_group_norm_apply_padded(const sdk_group_norm_args* a, int32_t silu, void* y, int32_t ld_y,
                                            int32_t h, int32_t w, int32_t pad, sdk_stream_t stream) {
-  if (!a || !a->src0 || !a->scale || !a->shift || !y) return fail(SDK_EINVAL, "group_norm_apply: null pointer");
-  if (a->channels % 8 || a->c_split % 8 || a->c_split <= 0 || a->c_split > a->channels || ld_y % 8 ||
-      ld_y < a->channels)
-    return fail(SDK_EINVAL, "group_norm_apply: channels/c_split/ld_y must be multiples of 8");
-  if (a->c_split < a->channels && !a->src1) return fail(SDK_EINVAL, "group_norm_apply: concat without src1");
-  if (h <= 0 || w <= 0 || (int64_t)h * w != a->hw || pad < 0 || pad > 4)
-    return fail(SDK_EINVAL, "group_norm_apply_padded: h*w must equal hw, pad in [0, 4]");
-  const int64_t nvec = (int64_t)a->batch * (h + 2 * pad) * (w + 2 * pad) * (a->channels / 8);
-  if (nvec <= 0) return SDK_OK;
-  const int hp = h + 2 * pad, wp = w + 2 * pad;
-  if (gn_apply_flat(a, silu, y, ld_y, h, w, pad, (hipStream_t)stream)) return check_launch("gn_apply_flat");
-  const unsigned divm = (int64_t)wp * (a->channels / 8) < (1 << 24) ? pad_row_divm(wp * (a->channels / 8), a->channels / 8) : 0;
-  // the row form where it measured faster (the VAE decoder's >= 128x128 images: 206.6 -> 182.5 us at 128x128x512,
-  // 696.6 -> 677.8 at 512x512x128); the grid-stride form elsewhere (64x64x640 56.6 vs 58.9 us, 16x16 17.4 vs 19.4)
-  if (divm && (int64_t)h * w >= 128 * 128 && a->channels <= 4096 && hp <= 65535 && a->batch <= 65535) {
-    hipLaunchKernelGGL(gn_apply_pad_row_kernel, dim3(hp, a->batch), dim3(256), (size_t)a->channels * 8,
-                       (hipStream_t)stream, (const half_t*)a->src0, (const half_t*)a->src1, a->c_split, a->ld0, a->ld1,
-                       h, w, pad, a->channels, a->scale, a->shift, silu, (half_t*)y, ld_y, divm);
-    return check_launch("gn_apply_pad");
-  }
-  const int blocks = (int)std::min<int64_t>((nvec + 255) / 256, 8192);
-  hipLaunchKernelGGL(gn_apply_pad_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const half_t*)a->src0,
-                     (const half_t*)a->src1, a->c_split, a->ld0, a->ld1, h, w, pad, a->channels, a->scale, a->shift,
-                     silu, (half_t*)y, ld_y, nvec);
-  return check_launch("gn_apply_pad");
+  return gn_run(GnReq{"group_norm_apply_padded", a, false, true, false, true, h, w, pad, nullptr, 0, nullptr, 0, y, ld_y},
+                silu, stream);
 }
 
 extern "C" int sdk_group_norm_apply_ex(const sdk_group_norm_args* a, int32_t silu, const float* post_bias,
@@ -1175,95 +1275,22 @@ extern "C" int sdk_layer_norm(const void* x, void* y, int32_t rows, int32_t cols
   return check_launch("layer_norm");
 }
 
-// GroupNorm (+ SiLU) end to end: statistics and apply, written contiguous (pad = 0) or into a
-// zero-bordered [B][h+2pad][w+2pad][ld_y] image.  Statistics: merged from the producing convs'
-// per-chunk partials when given (part0, and part1 for a concat), else one fused statistics+apply
-// launch at the smallest levels (hw <= SDK_GN_APPLY_FUSED_MAX_HW), else the statistics pass; then
-// the apply pass.  a->scale / a->shift (and a->workspace for the statistics pass) as for
-// sdk_group_norm_affine.
-static const int g_gn_apply_fused_max_hw = [] {
-  const char* e = getenv("SDK_GN_APPLY_FUSED_MAX_HW");
-  return e ? atoi(e) : 64;
-}();
-// largest image (h*w) whose GroupNorm-from-partials runs as one gn_apply_part_kernel launch
-static const int g_gn_part_fused_max_hw = [] {
-  const char* e = getenv("SDK_GN_PART_FUSED_MAX_HW");
-  return e ? atoi(e) : 256;
-}();
-
 extern "C" int sdk_group_norm_finalize(const sdk_group_norm_args* a, const float* part0, int32_t nch0,
                                        const float* part1, int32_t nch1, sdk_stream_t stream) {
-  if (!a || !a->src0 || !a->scale || !a->shift) return fail(SDK_EINVAL, "group_norm_finalize: null pointer");
-  if (a->channels % 8 || a->groups <= 0 || a->channels % a->groups || a->c_split % 8 || a->c_split <= 0 ||
-      a->c_split > a->channels)
-    return fail(SDK_EINVAL, "group_norm_finalize: channels/c_split must be multiples of 8, channels % groups == 0");
-  const bool concat = a->c_split < a->channels;
-  const bool parts = part0 && (!concat || part1);
-  if (!parts) return sdk_group_norm_affine(a, stream);
-  if (nch0 <= 0 || a->hw % nch0 || (concat && (nch1 <= 0 || a->hw % nch1)))
-    return fail(SDK_EINVAL, "group_norm_finalize: partial chunks must divide hw");
-  if (a->batch <= 0) return SDK_OK;
-  hipLaunchKernelGGL(gn_finalize_part_kernel, dim3(a->groups, a->batch), dim3(256), 0, (hipStream_t)stream,
-                     (const float2*)part0, nch0, (const float2*)part1, nch1, a->c_split, a->hw, a->channels, a->groups,
-                     a->eps, a->gamma, a->beta, a->scale, a->shift);
-  return check_launch("gn_finalize_part");
+  return gn_run(GnReq{"group_norm_finalize", a, true, false, false, false, 0, 0, 0, part0, nch0, part1, nch1, nullptr, 0},
+                0, stream);
 }
 
+// GroupNorm (+ SiLU) end to end: statistics and apply, written contiguous (pad = 0) or into a
+// zero-bordered [B][h+2pad][w+2pad][ld_y] image.  Statistics: merged from the producing convs'
+// per-chunk partials when given (part0, and part1 for a concat), else the statistics pass; at the
+// smallest levels statistics and apply are one launch (gn_plan).  a->scale / a->shift (and a->workspace
+// for the statistics pass) as for sdk_group_norm_affine.
 extern "C" int sdk_group_norm(const sdk_group_norm_args* a, int32_t silu, void* y, int32_t ld_y, int32_t h, int32_t w,
                               int32_t pad, const float* part0, int32_t nch0, const float* part1, int32_t nch1,
                               sdk_stream_t stream) {
-  if (!a || !a->src0 || !y) return fail(SDK_EINVAL, "group_norm: null pointer");
-  if (a->channels % 8 || a->groups <= 0 || a->channels % a->groups || a->c_split % 8 || a->c_split <= 0 ||
-      a->c_split > a->channels || ld_y % 8 || ld_y < a->channels)
-    return fail(SDK_EINVAL, "group_norm: channels/c_split/ld_y must be multiples of 8, channels % groups == 0");
-  if (a->channels / a->groups > 256) return fail(SDK_EINVAL, "group_norm: > 256 channels per group");
-  if (a->c_split < a->channels && !a->src1) return fail(SDK_EINVAL, "group_norm: concat without src1");
-  if (a->ld0 % 8 || (a->c_split < a->channels && a->ld1 % 8)) return fail(SDK_EINVAL, "group_norm: ld % 8");
-  if (h <= 0 || w <= 0 || (int64_t)h * w != a->hw || pad < 0 || pad > 4)
-    return fail(SDK_EINVAL, "group_norm: h*w must equal hw, pad in [0, 4]");
-  const bool concat = a->c_split < a->channels;
-  const bool parts = part0 && (!concat || part1);
-  if (parts && (nch0 <= 0 || a->hw % nch0 || (concat && (nch1 <= 0 || a->hw % nch1))))
-    return fail(SDK_EINVAL, "group_norm: partial chunks must divide hw");
-  hipStream_t s = (hipStream_t)stream;
-  const int gps = gn_fused_gps(a->channels, a->groups);
-  if (!parts && gps > 0 && a->hw <= g_gn_apply_fused_max_hw && a->batch > 0) {
-    hipLaunchKernelGGL(gn_stats_fused_kernel<true>, dim3(a->groups / gps, a->batch), dim3(GNF_T), 0, s,
-                       (const half_t*)a->src0, (const half_t*)a->src1, a->c_split, a->ld0, a->ld1, a->hw, a->channels,
-                       a->channels / a->groups, gps, a->eps, a->gamma, a->beta, nullptr, nullptr, silu, (half_t*)y,
-                       ld_y, h, w, pad);
-    return check_launch("gn_fused_apply");
-  }
-  const int pgps = gn_part_gps(a->channels, a->groups);
-  if (parts && pgps > 0 && a->hw <= g_gn_part_fused_max_hw && a->batch > 0 && nch0 <= GNP_MAXCH &&
-      (!concat || nch1 <= GNP_MAXCH)) {
-    const int cs = pgps * (a->channels / a->groups), slices = a->groups / pgps;
-    const int npix = (h + 2 * pad) * (w + 2 * pad);
-    // ~8 vectors per thread (one round of loads in flight), at least ~512 workgroups when the image allows
-    int splits = std::max(1, (npix * (cs / 8) + 2047) / 2048);
-    const int want = (512 + slices * a->batch - 1) / (slices * a->batch);
-    splits = std::min(std::max(splits, want), std::max(1, npix / 16));
-    const int rows_per = (npix + splits - 1) / splits;
-    splits = (npix + rows_per - 1) / rows_per;
-    hipLaunchKernelGGL(gn_apply_part_kernel, dim3(slices, a->batch, splits), dim3(256), 0, s, (const float2*)part0,
-                       nch0, (const float2*)part1, nch1, (const half_t*)a->src0, (const half_t*)a->src1, a->c_split,
-                       a->ld0, a->ld1, h, w, pad, a->channels, a->channels / a->groups, pgps, a->eps, a->gamma,
-                       a->beta, a->scale, a->shift, silu, (half_t*)y, ld_y, rows_per);
-    return check_launch("gn_apply_part");
-  }
-  if (!a->scale || !a->shift) return fail(SDK_EINVAL, "group_norm: scale/shift buffers needed");
-  if (parts) {
-    if (a->batch > 0) {
-      hipLaunchKernelGGL(gn_finalize_part_kernel, dim3(a->groups, a->batch), dim3(256), 0, s, (const float2*)part0,
-                         nch0, (const float2*)part1, nch1, a->c_split, a->hw, a->channels, a->groups, a->eps, a->gamma,
-                         a->beta, a->scale, a->shift);
-      if (int e = check_launch("gn_finalize_part")) return e;
-    }
-  } else if (int e = sdk_group_norm_affine(a, stream)) {
-    return e;
-  }
-  return pad ? sdk_group_norm_apply_padded(a, silu, y, ld_y, h, w, pad, stream)
-             : sdk_group_norm_apply(a, silu, y, ld_y, stream);
+  return gn_run(GnReq{"group_norm", a, true, true, true, true, h, w, pad, part0, nch0, part1, nch1, y, ld_y}, silu,
+                stream);
 }
 
 static int pad_image(const char* what, int sh, const void* x, int32_t ld_x, void* y, int32_t batch, int32_t h, int32_t w,
@@ -1299,24 +1326,14 @@ extern "C" int sdk_group_norm_film(const sdk_group_norm_args* a, const float* fi
                                    int32_t silu, void* y, int32_t ld_y, int32_t h, int32_t w, int32_t pad,
                                    const float* part0, int32_t nch0, const float* part1, int32_t nch1,
                                    sdk_stream_t stream) {
-  if (!a || !a->src0 || !y || !a->scale || !a->shift || !film)
-    return fail(SDK_EINVAL, "group_norm_film: null pointer (scale / shift buffers are required)");
-  if (a->channels <= 0 || a->channels % 8 || a->groups <= 0 || a->channels % a->groups || a->c_split % 8 ||
-      a->c_split <= 0 || a->c_split > a->channels || ld_y % 8 || ld_y < a->channels)
-    return fail(SDK_EINVAL, "group_norm_film: channels/c_split/ld_y must be multiples of 8, channels % groups == 0");
+  if (!a || !film) return fail(SDK_EINVAL, "group_norm_film: null pointer");
   if (film_off < 0 || film_ld < film_off + 2 * a->channels)
     return fail(SDK_EINVAL, "group_norm_film: film rows hold 2*channels values from film_off");
-  if (h <= 0 || w <= 0 || (int64_t)h * w != a->hw || pad < 0 || pad > 4)
-    return fail(SDK_EINVAL, "group_norm_film: h*w must equal hw, pad in [0, 4]");
-  if (a->batch <= 0) return SDK_OK;
-  if ((int64_t)a->batch * a->channels >= (1LL << 31)) return fail(SDK_EINVAL, "group_norm_film: batch*channels");
-  if (int e = sdk_group_norm_finalize(a, part0, nch0, part1, nch1, stream)) return e;
-  const int n = a->batch * a->channels;
-  hipLaunchKernelGGL(gn_film_fold_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a->scale, a->shift,
-                     film, film_ld, film_off, a->channels, n);
-  if (int e = check_launch("gn_film_fold")) return e;
-  return pad ? sdk_group_norm_apply_padded(a, silu, y, ld_y, h, w, pad, stream)
-             : sdk_group_norm_apply(a, silu, y, ld_y, stream);
+  if (a->batch > 0 && (int64_t)a->batch * a->channels >= (1LL << 31))
+    return fail(SDK_EINVAL, "group_norm_film: batch*channels");
+  const GnFilm fold{film, film_ld, film_off};
+  return gn_run(GnReq{"group_norm_film", a, true, true, false, true, h, w, pad, part0, nch0, part1, nch1, y, ld_y}, silu,
+                stream, &fold);
 }
 
 extern "C" int sdk_group_norm_resample(const sdk_group_norm_args* a, int32_t mode, int32_t silu, int32_t h, int32_t w,

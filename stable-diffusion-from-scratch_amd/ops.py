@@ -623,7 +623,10 @@ def segment_softmax(s, nseg, seglen, scale, ld_p=None, out=None):
 
 # --------------------------------------------------------------------------- normalisation
 
-def _gn_args(x):
+def _gn_args(x, gamma=None, beta=None, eps=0.0, groups=32, gn=None):
+    """``(GroupNormArgs, (B, H, W, C), device, gn)`` of x (a tensor or a 2-source concat pair).  With gamma / beta the
+    statistics side is filled in too: groups, eps, a workspace and fresh fp32 ``[B, C]`` scale / shift buffers
+    (returned as ``gn``); with ``gn`` = (scale, shift) those are the given affine."""
     a0, a1 = _as_pair(x)
     _need_cuda(a0, "group_norm")
     B, H, W, Ch = src_shape(x)
@@ -635,7 +638,51 @@ def _gn_args(x):
         args.ld1 = a1.stride(2)
     args.c_split = a0.shape[-1]
     args.batch, args.hw, args.channels = B, H * W, Ch
-    return args, (B, H, W, Ch), a0.device
+    if gamma is not None:
+        args.groups, args.eps = groups, eps
+        args.gamma, args.beta = gamma.data_ptr(), beta.data_ptr()
+        gn = (torch.empty(B, Ch, dtype=torch.float32, device=a0.device),
+              torch.empty(B, Ch, dtype=torch.float32, device=a0.device))
+        ws = WORKSPACE.get(lib().sdk_group_norm_workspace(B, H * W, Ch), a0.device)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    if gn is not None:
+        args.scale, args.shift = gn[0].data_ptr(), gn[1].data_ptr()
+    return args, (B, H, W, Ch), a0.device, gn
+
+
+def _producer_parts(x):
+    """(part0, nch0, part1, nch1) of the statistics the producing convs attached to x's sources, or
+    (None, 0, None, 0) unless every source carries current ones (a tensor modified in place since — its
+    version counter moved — no longer does)."""
+    srcs = [t for t in _as_pair(x) if t is not None]
+    parts = [getattr(t, GN_ATTR, None) for t in srcs]
+    parts = [pp if pp is not None and pp[2] == t._version else None for pp, t in zip(parts, srcs)]
+    if not all(pp is not None for pp in parts):
+        return None, 0, None, 0
+    p1, n1 = (parts[1][0], parts[1][1]) if len(parts) > 1 else (None, 0)
+    return parts[0][0], parts[0][1], p1, n1
+
+
+def group_norm_plan(x, *, groups=32, pad=0, stats=True, apply=True, parts=None, single_launch=True):
+    """The launches GroupNorm takes on x, decided on the host by the planner every GroupNorm entry point routes
+    through (``sdk_group_norm_plan``): ``{"stats": "given" | "slice" | "chunked" | "parts", "apply": "none" |
+    "in_stats" | "flat" | "row" | "stride", "launches": n, "workspace_bytes": n}``.  ``stats`` / ``apply``: what the
+    call computes (``group_norm``: both; ``group_norm_affine`` / ``group_norm_scale_shift``: statistics only;
+    ``group_norm_apply``: apply only).  ``parts``: (nch0, nch1) chunk counts of producer statistics, 0 / False for
+    none, None = whatever x's sources carry, as ``group_norm`` uses them.  ``single_launch=False``:
+    ``group_norm_film``."""
+    args, (B, H, W, Ch), _, _ = _gn_args(x)
+    args.groups = groups
+    args.scale = args.shift = args.src0          # only their presence counts
+    if parts is None:
+        _, n0, _, n1 = _producer_parts(x)
+    else:
+        n0, n1 = (parts, parts) if isinstance(parts, int) else parts
+    info = _lib.GroupNormPlanInfo()
+    check(lib().sdk_group_norm_plan(C.byref(args), int(stats), int(apply), H, W, pad, int(n0), int(n1),
+                                    int(single_launch), C.byref(info)), "group_norm_plan")
+    return {"stats": _lib.GN_STATS[info.stats], "apply": _lib.GN_APPLY[info.apply], "launches": info.launches,
+            "workspace_bytes": info.workspace_bytes}
 
 
 # zero-bordered GN+SiLU outputs for pad-0 3x3 convs (mask-free gather); 0 = the masked pad-1 path
@@ -650,8 +697,7 @@ def gn_conv_pad():
 def group_norm_apply(x, gn, silu=True, out=None, pad=0):
     """y = silu?(x*scale + shift) — the normalised (possibly concatenated) input, contiguous NHWC.
     ``pad`` > 0 writes it into a zero-bordered [B, H+2pad, W+2pad, C] image for a pad-0 3x3 conv."""
-    args, (B, H, W, Ch), dev = _gn_args(x)
-    args.scale, args.shift = gn[0].data_ptr(), gn[1].data_ptr()
+    args, (B, H, W, Ch), dev, _ = _gn_args(x, gn=gn)
     y = _claim(out) if out is not None else torch.empty(B, H + 2 * pad, W + 2 * pad, Ch, dtype=torch.float16,
                                                           device=dev)
     if PROFILER.active:
@@ -669,8 +715,7 @@ def group_norm_apply(x, gn, silu=True, out=None, pad=0):
 
 def group_norm_apply_ex(x, gn, silu=True, post_bias=None, residual=None):
     """y = silu?(x*scale + shift) + post_bias[b, c] + residual (DDPM C1 post-activation GroupNorm)."""
-    args, (B, H, W, Ch), dev = _gn_args(x)
-    args.scale, args.shift = gn[0].data_ptr(), gn[1].data_ptr()
+    args, (B, H, W, Ch), dev, _ = _gn_args(x, gn=gn)
     y = torch.empty(B, H, W, Ch, dtype=torch.float16, device=dev)
     pb_ld = 0
     if post_bias is not None:
@@ -733,94 +778,41 @@ def gelu(x):
     return y
 
 
-def group_norm_silu(x, gamma, beta, eps, groups=32):
-    """GroupNorm + SiLU materialised once (stats pass + apply pass) — the input of a 3x3 conv."""
-    return group_norm_apply(x, group_norm_affine(x, gamma, beta, eps, groups), silu=True)
-
-
 def group_norm_scale_shift(x, gamma, beta, eps, groups=32):
     """Per-(batch, channel) fp32 (scale, shift) [B, C] of GroupNorm(x) from the statistics its producing
     convs emitted (else a statistics pass) — for a 3x3 conv that applies GroupNorm + SiLU to its own
     prologue (``conv2d(gn=(scale, shift), silu=True)`` on the register-staged kernel), so the normalised
     tensor is never written (``sdk_group_norm_finalize``)."""
-    args, (B, H, W, Ch), dev = _gn_args(x)
-    args.groups, args.eps = groups, eps
-    args.gamma, args.beta = gamma.data_ptr(), beta.data_ptr()
-    scale = torch.empty(B, Ch, dtype=torch.float32, device=dev)
-    shift = torch.empty(B, Ch, dtype=torch.float32, device=dev)
-    args.scale, args.shift = scale.data_ptr(), shift.data_ptr()
-    ws = WORKSPACE.get(lib().sdk_group_norm_workspace(B, H * W, Ch), dev)
-    args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
-    srcs = [t for t in _as_pair(x) if t is not None]
-    parts = [getattr(t, GN_ATTR, None) for t in srcs]
-    parts = [pp if pp is not None and pp[2] == t._version else None for pp, t in zip(parts, srcs)]
-    p0 = p1 = None
-    n0 = n1 = 0
-    if all(pp is not None for pp in parts):
-        (p0, n0, _) = parts[0]
-        if len(parts) > 1:
-            (p1, n1, _) = parts[1]
+    args, _, _, gn = _gn_args(x, gamma, beta, eps, groups)
+    p0, n0, p1, n1 = _producer_parts(x)
     if PROFILER.active:
         PROFILER.begin("group_norm", None)
     check(lib().sdk_group_norm_finalize(C.byref(args), _ptr(p0), n0, _ptr(p1), n1, _stream()), "group_norm_finalize")
     if PROFILER.active:
         PROFILER.end()
-    return scale, shift
+    return gn
 
 
 def group_norm_affine(x, gamma, beta, eps, groups=32):
     """Per-(batch, channel) (scale, shift) fp32 [B, C] of GroupNorm(x) for the conv prologue."""
-    a0, a1 = _as_pair(x)
-    _need_cuda(a0, "group_norm")
-    B, H, W, Ch = src_shape(x)
-    args = GroupNormArgs()
-    args.src0 = a0.data_ptr()
-    args.ld0 = a0.stride(2)
-    if a1 is not None:
-        args.src1 = a1.data_ptr()
-        args.ld1 = a1.stride(2)
-    args.c_split = a0.shape[-1]
-    args.batch, args.hw, args.channels, args.groups, args.eps = B, H * W, Ch, groups, eps
-    args.gamma = gamma.data_ptr()
-    args.beta = beta.data_ptr()
-    scale = torch.empty(B, Ch, dtype=torch.float32, device=a0.device)
-    shift = torch.empty(B, Ch, dtype=torch.float32, device=a0.device)
-    args.scale, args.shift = scale.data_ptr(), shift.data_ptr()
-    need = lib().sdk_group_norm_workspace(B, H * W, Ch)
-    ws = WORKSPACE.get(need, a0.device)
-    args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    args, _, _, gn = _gn_args(x, gamma, beta, eps, groups)
     if PROFILER.active:
         PROFILER.begin("group_norm", None)
     check(lib().sdk_group_norm_affine(C.byref(args), _stream()), "group_norm_affine")
     if PROFILER.active:
         PROFILER.end()
-    return scale, shift
+    return gn
 
 
 def group_norm(x, gamma, beta, eps, groups=32, silu=True, pad=0, out=None):
-    """GroupNorm (+ SiLU) end to end in one C call: statistics and apply, written contiguous or
-    zero-bordered (``pad``) for a pad-0 3x3 conv.  At the UNet's small levels one fused launch;
-    elsewhere the statistics pass then the apply pass (``sdk_group_norm``)."""
-    args, (B, H, W, Ch), dev = _gn_args(x)
-    args.groups, args.eps = groups, eps
-    args.gamma, args.beta = gamma.data_ptr(), beta.data_ptr()
-    scale = torch.empty(B, Ch, dtype=torch.float32, device=dev)
-    shift = torch.empty(B, Ch, dtype=torch.float32, device=dev)
-    args.scale, args.shift = scale.data_ptr(), shift.data_ptr()
-    ws = WORKSPACE.get(lib().sdk_group_norm_workspace(B, H * W, Ch), dev)
-    args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    """GroupNorm (+ SiLU) end to end in one C call: statistics (from the producing convs' partials when every
+    source carries them) and apply, written contiguous or zero-bordered (``pad``) for a pad-0 3x3 conv.  At the
+    UNet's small levels one fused launch; elsewhere the statistics pass then the apply pass (``sdk_group_norm``;
+    ``group_norm_plan`` names the forms)."""
+    args, (B, H, W, Ch), dev, gn = _gn_args(x, gamma, beta, eps, groups)
     y = _claim(out) if out is not None else torch.empty(B, H + 2 * pad, W + 2 * pad, Ch, dtype=torch.float16,
                                                           device=dev)
-    # statistics the producing convs emitted (every source must carry them)
-    srcs = [t for t in _as_pair(x) if t is not None]
-    parts = [getattr(t, GN_ATTR, None) for t in srcs]
-    parts = [pp if pp is not None and pp[2] == t._version else None for pp, t in zip(parts, srcs)]
-    p0 = p1 = None
-    n0 = n1 = 0
-    if all(pp is not None for pp in parts):
-        (p0, n0, _) = parts[0]
-        if len(parts) > 1:
-            (p1, n1, _) = parts[1]
+    p0, n0, p1, n1 = _producer_parts(x)
     if PROFILER.active:
         PROFILER.begin("group_norm", None)
     check(lib().sdk_group_norm(C.byref(args), 1 if silu else 0, _ptr(y), y.shape[-1], H, W, pad, _ptr(p0), n0,
@@ -830,34 +822,15 @@ def group_norm(x, gamma, beta, eps, groups=32, silu=True, pad=0, out=None):
     return y
 
 
-def _producer_parts(x):
-    """(part0, nch0, part1, nch1) of the statistics the producing convs attached to x's sources, or
-    (None, 0, None, 0) unless every source carries current ones."""
-    srcs = [t for t in _as_pair(x) if t is not None]
-    parts = [getattr(t, GN_ATTR, None) for t in srcs]
-    parts = [pp if pp is not None and pp[2] == t._version else None for pp, t in zip(parts, srcs)]
-    if not all(pp is not None for pp in parts):
-        return None, 0, None, 0
-    p1, n1 = (parts[1][0], parts[1][1]) if len(parts) > 1 else (None, 0)
-    return parts[0][0], parts[0][1], p1, n1
-
-
 def group_norm_film(x, gamma, beta, eps, film, film_off, groups=32, silu=True, pad=0, out=None):
     """GroupNorm with FiLM conditioning (+ SiLU): ``silu?(GN(x) * (1 + f) + g)`` with ``f = film[:, off:off+C]``,
     ``g = film[:, off+C:off+2C]`` (fp32 ``[B, ld]``, the batched ``emb_layers`` GEMM), folded into the
     per-(batch, channel) affine so x is read once and y written once (``sdk_group_norm_film``)."""
-    args, (B, H, W, Ch), dev = _gn_args(x)
+    args, (B, H, W, Ch), dev, gn = _gn_args(x, gamma, beta, eps, groups)
     _need_cuda(film, "group_norm_film film", torch.float32)
     if film.dim() != 2 or film.shape[0] != B or film.stride(1) != 1 or film_off < 0 or \
             film_off + 2 * Ch > film.shape[1]:
         raise ValueError(f"sd_amd.group_norm_film: film {tuple(film.shape)} has no [{B}, {film_off}:{film_off}+2*{Ch}]")
-    args.groups, args.eps = groups, eps
-    args.gamma, args.beta = gamma.data_ptr(), beta.data_ptr()
-    scale = torch.empty(B, Ch, dtype=torch.float32, device=dev)
-    shift = torch.empty(B, Ch, dtype=torch.float32, device=dev)
-    args.scale, args.shift = scale.data_ptr(), shift.data_ptr()
-    ws = WORKSPACE.get(lib().sdk_group_norm_workspace(B, H * W, Ch), dev)
-    args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
     y = _claim(out) if out is not None else torch.empty(B, H + 2 * pad, W + 2 * pad, Ch, dtype=torch.float16,
                                                           device=dev)
     p0, n0, p1, n1 = _producer_parts(x)
@@ -878,11 +851,9 @@ def group_norm_resample(x, gn, mode, silu=True, pad=0, act=True, raw=True):
     """One read of x, two outputs (``sdk_group_norm_resample``): ``(resample(silu?(x*scale + shift)) zero-bordered
     by pad, resample(x) contiguous)``; ``mode`` 'down' = avg-pool 2x2 stride 2 (odd H / W floor), 'up' = nearest x2.
     ``gn`` = (scale, shift) fp32 ``[B, C]`` or None (raw only); an output not asked for is None."""
-    args, (B, H, W, Ch), dev = _gn_args(x)
+    args, (B, H, W, Ch), dev, _ = _gn_args(x, gn=gn)
     if gn is None:
         act = False
-    else:
-        args.scale, args.shift = gn[0].data_ptr(), gn[1].data_ptr()
     if not act and not raw:
         raise ValueError("sd_amd.group_norm_resample: no output asked for")
     Ho, Wo = (H // 2, W // 2) if mode == "down" else (2 * H, 2 * W)
