@@ -452,6 +452,49 @@ typedef struct {
 
 int sdk_masked_q_sample(const sdk_masked_q_args* a, sdk_stream_t stream);
 
+/* Classifier-free-guidance combine on its own (ddim.py:178): out = e_uncond + guidance*(e_cond - e_uncond),
+ * the same two fp32 operations as the combine fused into sdk_ddim_step, so sdk_cfg_combine followed by an
+ * unguided step gives the guided step's bits (a score corrector needs the combined e as a tensor).  Any
+ * n >= 1; 16-byte accesses when every pointer is 16-byte aligned, scalar otherwise and for the tail.
+ * out may alias either input. */
+int sdk_cfg_combine(const float* e_uncond, const float* e_cond, float* out, int64_t n, float guidance,
+                    sdk_stream_t stream);
+
+/* DDIM update with the sampler options (ddim.py:144-204); sdk_ddim_step and sdk_ddim_xprev launch the same
+ * kernel with everything after `step` zero.
+ *   step        the fields of sdk_ddim_step.
+ *   pred_x0_in  1: step.pred_x0 is an INPUT (sdk_ddim_xprev); step.x is then read only with v_param.
+ *   keep        noise dropout (ddim.py:201-202), one byte (0 / 1) per element, or NULL; needs step.noise.  The
+ *               noise term becomes ((sigma*noise)*temperature) * (keep*drop_scale), drop_scale = fp32(1/(1-p)):
+ *               a multiply as in F.dropout, never a select, so the signed zeros match.
+ *   blend       with blend.mask != NULL the known-region blend that opens the NEXT loop iteration
+ *               (ddim.py:146-147) is applied to x_prev: blend.out = (sqrt_acp*x0 + sqrt_1m_acp*noise)*mask +
+ *               (1 - mask)*x_prev, sqrt_acp / sqrt_1m_acp the model's schedule entries at the next timestep;
+ *               blend.img and blend.n are ignored, the mask is read as by sdk_masked_q_sample.  step.x_prev
+ *               and pred_x0 hold the unblended values.  blend.out may alias step.x.
+ * Any n >= 1; 16-byte accesses when every pointer is 16-byte aligned (keep: 4-byte), scalar otherwise and
+ * for the tail. */
+typedef struct {
+  sdk_ddim_args step;
+  int32_t pred_x0_in;
+  float drop_scale;
+  const uint8_t* keep;
+  sdk_masked_q_args blend;
+} sdk_ddim_ex_args;
+
+int sdk_ddim_step_ex(const sdk_ddim_ex_args* a, sdk_stream_t stream);
+
+/* sdk_posterior_step with noise dropout (ldm/diffusion/ddpm.py:1621-1636): step 4 becomes
+ * x_prev = mean + ((nonzero*sigma) * ((noise*temperature) * (keep*drop_scale))); keep / drop_scale as in
+ * sdk_ddim_ex_args, keep NULL: sdk_posterior_step (which launches the same kernel). */
+typedef struct {
+  sdk_posterior_args step;
+  const uint8_t* keep;
+  float drop_scale;
+} sdk_posterior_ex_args;
+
+int sdk_posterior_step_ex(const sdk_posterior_ex_args* a, sdk_stream_t stream);
+
 /* sdk_nchw_to_nhwc (scale 1) of torch.cat(src, 1) without the concatenated fp32 tensor
  * (DiffusionWrapper.forward 'concat' / 'hybrid', Diffusion/ddpm.py:51-63): nsrc (1..4) NCHW fp32 sources
  * [batch][channels[i]][hw] -> y NHWC fp16 [batch][hw][c_pad]; source i lands at channel offset

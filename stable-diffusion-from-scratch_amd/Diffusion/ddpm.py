@@ -16,8 +16,13 @@ with the CompVis scaling ``z / scale_factor`` (``ldm/diffusion/ddpm.py:1095``;
 ``use_graphs(True)`` makes ``DiffusionWrapper.forward`` replay one HIP graph per UNet call
 (``graphs.GraphedUNet``) — same chain apply_model → DiffusionWrapper.forward → UNetModel,
 one hipGraphLaunch per step instead of ~600 kernel launches.
-Refused (NotImplementedError): ``score_corrector``, ``noise_dropout``, ``return_codebook_ids``,
-``shorten_cond_schedule``, ``progressive_denoising``.
+``score_corrector`` / ``noise_dropout`` (``ldm/diffusion/ddpm.py:1544-1546,1623-1624``; the keep mask is drawn
+with torch and multiplied in by ``sdk_posterior_step_ex``), ``progressive_denoising`` (``:1641-1739``),
+``shorten_cond_schedule`` (``make_cond_schedule`` ``:676-681`` and the ``q_sample`` of the conditioning in both
+loops, Gaussian noise) and ``sample_log`` (``:1814-1826``) follow the reference; the hooks ``noise_fn``,
+``q_noise_fn``, ``dropout_fn`` and ``cond_noise_fn`` supply recorded draws.
+Refused (NotImplementedError): ``return_codebook_ids`` (the reference itself raises on it), and the four options
+above on a model that is not on the GPU (HIP kernels, no CPU fallback).
 Out of scope (training / Lightning): losses, EMA, optimisers, data, logging.
 """
 from __future__ import annotations
@@ -141,6 +146,16 @@ class LatentDiffusion(nn.Module):
         self.log_every_t = log_every_t
         self.register_schedule(given_betas=given_betas, beta_schedule=beta_schedule, timesteps=timesteps,
                                linear_start=linear_start, linear_end=linear_end, cosine_s=cosine_s)
+        if self.shorten_cond_schedule:
+            self.make_cond_schedule()
+
+    def make_cond_schedule(self):
+        """``ldm/diffusion/ddpm.py:676-681``: the conditioning's timestep per sampler timestep, the same torch
+        CPU calls (a host table: the loops index it with host ints)."""
+        with torch.device("cpu"):
+            self.cond_ids = torch.full(size=(self.num_timesteps,), fill_value=self.num_timesteps - 1, dtype=torch.long)
+            ids = torch.round(torch.linspace(0, self.num_timesteps - 1, self.num_timesteps_cond)).long()
+            self.cond_ids[:self.num_timesteps_cond] = ids
 
     def register_schedule(self, given_betas=None, beta_schedule="linear", timesteps=1000, linear_start=1e-4,
                           linear_end=2e-2, cosine_s=8e-3):
@@ -289,13 +304,31 @@ class LatentDiffusion(nn.Module):
         # stage 2 without noise: the noise term is (0·σ)·(0·T) = 0, x_prev = mean + 0
         return ops.posterior_step(x, None, th, self._host_tables(), stage=2, x_recon_in=x_recon)[0]
 
-    def _refuse(self, return_codebook_ids=False, score_corrector=None, noise_dropout=0.):
+    def _refuse(self, return_codebook_ids=False):
         if return_codebook_ids:
             raise NotImplementedError("sd_amd: return_codebook_ids is not implemented (the reference dropped it)")
-        if score_corrector is not None:
-            raise NotImplementedError("sd_amd: score_corrector is not implemented by the ancestral sampler")
-        if noise_dropout > 0:
-            raise NotImplementedError("sd_amd: noise_dropout is not implemented by the ancestral sampler")
+
+    @staticmethod
+    def _need_gpu(device, noise_dropout=0., score_corrector=None, **flags):
+        """Off the GPU these options stay NotImplementedError, as before they had kernels."""
+        for on, option in [(noise_dropout > 0, "noise_dropout"), (score_corrector is not None, "score_corrector")] + \
+                [(on, name) for name, on in flags.items()]:
+            if on:
+                ops.need_gpu_sampler(option, device)
+
+    def _model_out(self, x, c, t, score_corrector=None, corrector_kwargs=None):
+        """``apply_model`` and the optional ``score_corrector.modify_score`` (``ldm/diffusion/ddpm.py:1542-1546``)."""
+        model_out = self._f32(self.apply_model(x, t, c))
+        if score_corrector is None:
+            return model_out
+        if self.parameterization != "eps":
+            raise AssertionError(f"sd_amd: score_corrector needs an eps model (ddpm.py:1545), this one is "
+                                 f"'{self.parameterization}'")
+        out = score_corrector.modify_score(self, model_out, x, t, c, **(corrector_kwargs or {}))
+        if not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or out.shape != x.shape:
+            raise ValueError("sd_amd: score_corrector.modify_score must return a CUDA fp32 tensor of x's shape "
+                             f"{tuple(x.shape)}")
+        return out.contiguous()
 
     def _quantizer(self):
         q = getattr(getattr(self, "first_stage_model", None), "quantize", None)
@@ -317,10 +350,11 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def p_mean_variance(self, x, c, t, clip_denoised: bool, return_codebook_ids=False, quantize_denoised=False,
                         return_x0=False, score_corrector=None, corrector_kwargs=None):
-        self._refuse(return_codebook_ids, score_corrector)
+        self._refuse(return_codebook_ids)
+        self._need_gpu(x.device, score_corrector=score_corrector)
         x = self._f32(x)
         th = self._host_t(t, x.shape[0])
-        model_out = self._f32(self.apply_model(x, t, c))
+        model_out = self._model_out(x, c, t, score_corrector, corrector_kwargs)
         x_recon = self._x_recon(x, model_out, th, clip_denoised, quantize_denoised)
         out = (self._posterior_mean(x_recon, x, th), self._bcast(self.posterior_variance, th, x),
                self._bcast(self.posterior_log_variance_clipped, th, x))
@@ -329,24 +363,33 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def p_sample(self, x, c, t, clip_denoised=False, repeat_noise=False, return_codebook_ids=False,
                  quantize_denoised=False, return_x0=False, temperture=1., noise_dropout=0., score_corrector=None,
-                 corrector_kwargs=None, temperature=None, noise=None, t_host=None):
+                 corrector_kwargs=None, temperature=None, noise=None, t_host=None, keep=None):
         """One ancestral step x_t → x_{t-1}.  ``temperture`` is the reference's spelling; ``temperature``
-        (when given) overrides it.  Extensions: ``noise`` (recorded noise instead of a fresh draw) and
+        (when given) overrides it.  Extensions: ``noise`` (recorded noise instead of a fresh draw), ``keep`` (the
+        keep mask of ``noise_dropout``, one byte per element, instead of a Bernoulli(1 − p) draw) and
         ``t_host`` (``t`` as host ints, saving the device read of ``t``)."""
-        self._refuse(return_codebook_ids, score_corrector, noise_dropout)
+        self._refuse(return_codebook_ids)
         if self.parameterization not in ("eps", "x0"):
             raise NotImplementedError(f"sd_amd: the ancestral sampler takes eps / x0 models, not "
                                       f"'{self.parameterization}'")
+        if not 0.0 <= float(noise_dropout) <= 1.0:
+            raise ValueError(f"sd_amd: noise_dropout must be in [0, 1], got {noise_dropout}")
+        self._need_gpu(x.device, noise_dropout, score_corrector)
         temp = float(temperture if temperature is None else temperature)
         x = self._f32(x)
         th = self._host_t(t if t_host is None else t_host, x.shape[0])
-        model_out = self._f32(self.apply_model(x, t, c))
+        model_out = self._model_out(x, c, t, score_corrector, corrector_kwargs)
         if noise is None:
             from ..DDIM.diffusion_modules import noise_like
             noise = noise_like(x.shape, x.device, repeat_noise)
         noise = noise.to(device=x.device, dtype=torch.float32).contiguous()
         tab = self._host_tables()
         kw = dict(temperature=temp)
+        if noise_dropout > 0:
+            # ldm/diffusion/ddpm.py:1623-1624: F.dropout of noise·temperature
+            kw["keep"] = keep if keep is not None else \
+                torch.empty(x.shape, dtype=torch.uint8, device=x.device).bernoulli_(1.0 - float(noise_dropout))
+            kw["drop_p"] = float(noise_dropout)
         if not quantize_denoised:
             x_prev, x0 = ops.posterior_step(x, model_out, th, tab, noise=noise, clip=clip_denoised,
                                             x0_param=self.parameterization == "x0", want_x_recon=return_x0, **kw)
@@ -355,29 +398,22 @@ class LatentDiffusion(nn.Module):
             x_prev, _ = ops.posterior_step(x, None, th, tab, noise=noise, stage=2, x_recon_in=x0, **kw)
         return (x_prev, x0) if return_x0 else x_prev
 
-    def progressive_denoising(self, *args, **kwargs):
-        raise NotImplementedError("sd_amd: progressive_denoising is not implemented (use p_sample_loop)")
-
-    @torch.no_grad()
-    def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None,
-                      timesteps=None, quantize_denoised=False, mask=None, x0=None, img_callback=None, start_T=None,
-                      log_every_t=None, temperature=1., noise_fn=None, q_noise_fn=None):
-        """``ldm/diffusion/ddpm.py:1745-1793``.  Extensions: ``temperature``, and the hooks
-        ``noise_fn(i, shape)`` / ``q_noise_fn(i, shape)`` that supply the step noise and the q_sample
-        noise of the mask blend at timestep ``i`` (reproducible runs, as DDIMSampler's ``noise_fn``)."""
-        if getattr(self, "shorten_cond_schedule", False):
-            raise NotImplementedError("sd_amd: shorten_cond_schedule (num_timesteps_cond > 1) is not implemented")
+    def _ancestral_loop(self, cond, shape, x_T, timesteps, temps, progressive, quantize_denoised, mask, x0,
+                        log_every_t, callback, img_callback, noise_dropout, score_corrector, corrector_kwargs,
+                        noise_fn, q_noise_fn, dropout_fn, cond_noise_fn):
+        """The loop of ``p_sample_loop`` (``ldm/diffusion/ddpm.py:1772-1789``) and ``progressive_denoising``
+        (``:1704-1737``): ``temps`` is a float or a list indexed by timestep; ``progressive`` collects the
+        ``x0_partial``s instead of the images."""
         if not log_every_t:
             log_every_t = self.log_every_t
         device = self.betas.device
+        shorten = getattr(self, "shorten_cond_schedule", False)
+        self._need_gpu(device, noise_dropout, score_corrector, progressive_denoising=progressive,
+                       shorten_cond_schedule=shorten)
         b = shape[0]
         img = torch.randn(tuple(shape), device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
         img = img.contiguous()
-        intermediates = [img]
-        if timesteps is None:
-            timesteps = self.num_timesteps
-        if start_T is not None:
-            timesteps = min(timesteps, start_T)
+        intermediates = [] if progressive else [img]
         if mask is not None:
             if x0 is None:
                 raise ValueError("sd_amd: mask needs x0 (the known region's latent)")
@@ -387,22 +423,87 @@ class LatentDiffusion(nn.Module):
             x0 = x0.to(device=device, dtype=torch.float32)
         if quantize_denoised:
             self._quantizer()
+        if shorten:
+            if self.model.conditioning_key == "hybrid":
+                raise AssertionError("sd_amd: shorten_cond_schedule does not take hybrid conditioning "
+                                     "(ldm/diffusion/ddpm.py:1775)")
+            if not torch.is_tensor(cond):
+                raise ValueError("sd_amd: shorten_cond_schedule needs the conditioning as one tensor, got "
+                                 f"{type(cond).__name__}")
         tab = self._host_tables()
         for i in reversed(range(0, timesteps)):
             ts = torch.full((b,), i, device=device, dtype=torch.long)
-            img = self.p_sample(img, cond, ts, clip_denoised=self.clip_denoised, quantize_denoised=quantize_denoised,
-                                temperature=temperature, t_host=i,
-                                noise=noise_fn(i, img.shape) if noise_fn is not None else None)
+            if shorten:
+                # reassigned every iteration, exactly as the reference does (:1776-1777)
+                cn = cond_noise_fn(i, cond.shape) if cond_noise_fn is not None else torch.randn_like(cond)
+                cond = self.q_sample(cond, int(self.cond_ids[i]), noise=cn)
+            out = self.p_sample(img, cond, ts, clip_denoised=self.clip_denoised, quantize_denoised=quantize_denoised,
+                                return_x0=progressive, t_host=i, noise_dropout=noise_dropout,
+                                temperature=temps[i] if isinstance(temps, (list, tuple)) else temps,
+                                score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,
+                                noise=noise_fn(i, img.shape) if noise_fn is not None else None,
+                                keep=dropout_fn(i, img.shape) if dropout_fn is not None else None)
+            img, x0_partial = out if progressive else (out, None)
             if mask is not None:
                 qn = q_noise_fn(i, img.shape) if q_noise_fn is not None else torch.randn_like(x0)
                 img = ops.masked_q_sample(x0, qn.to(device=device, dtype=torch.float32), mask, img, i,
                                           tab["sqrt_acp"], tab["sqrt_1m_acp"], out=img)
             if i % log_every_t == 0 or i == timesteps - 1:
-                intermediates.append(img)
+                intermediates.append(x0_partial if progressive else img)
             if callback:
                 callback(i)
             if img_callback:
                 img_callback(img, i)
+        return img, intermediates
+
+    @staticmethod
+    def _trim_cond(cond, batch_size):
+        if cond is None:
+            return None
+        if isinstance(cond, dict):
+            return {key: cond[key][:batch_size] if not isinstance(cond[key], list) else
+                    list(map(lambda x: x[:batch_size], cond[key])) for key in cond}
+        return [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+
+    @torch.no_grad()
+    def progressive_denoising(self, cond, shape, verbose=True, callback=None, quantize_denoised=False,
+                              img_callback=None, mask=None, x0=None, temperture=1., noise_dropout=0.,
+                              score_corrector=None, corrector_kwargs=None, batch_size=None, x_T=None, start_T=None,
+                              log_every_t=None, noise_fn=None, q_noise_fn=None, dropout_fn=None, cond_noise_fn=None):
+        """``ldm/diffusion/ddpm.py:1641-1739``: the ancestral loop that returns the ``x0_partial`` of the logged
+        steps.  ``batch_size`` prepends to ``shape``; ``temperture`` is a float or a list indexed by timestep.
+        The hooks are those of ``p_sample_loop``."""
+        if batch_size is not None:
+            shape = [batch_size] + list(shape)
+        else:
+            batch_size = shape[0]
+        cond = self._trim_cond(cond, batch_size)
+        timesteps = self.num_timesteps
+        if start_T is not None:
+            timesteps = min(timesteps, start_T)
+        temps = list(temperture) if isinstance(temperture, (list, tuple)) else float(temperture)
+        return self._ancestral_loop(cond, shape, x_T, timesteps, temps, True, quantize_denoised, mask, x0, log_every_t,
+                                    callback, img_callback, noise_dropout, score_corrector, corrector_kwargs,
+                                    noise_fn, q_noise_fn, dropout_fn, cond_noise_fn)
+
+    @torch.no_grad()
+    def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None,
+                      timesteps=None, quantize_denoised=False, mask=None, x0=None, img_callback=None, start_T=None,
+                      log_every_t=None, temperature=1., noise_fn=None, q_noise_fn=None, noise_dropout=0.,
+                      score_corrector=None, corrector_kwargs=None, dropout_fn=None, cond_noise_fn=None):
+        """``ldm/diffusion/ddpm.py:1745-1793``.  Extensions: ``temperature``, ``noise_dropout`` /
+        ``score_corrector`` / ``corrector_kwargs`` (passed to ``p_sample``), and the hooks ``noise_fn(i, shape)`` /
+        ``q_noise_fn(i, shape)`` / ``dropout_fn(i, shape)`` / ``cond_noise_fn(i, shape)`` that supply the step
+        noise, the q_sample noise of the mask blend, the dropout keep mask and the q_sample noise of the
+        shortened conditioning schedule at timestep ``i`` (reproducible runs, as DDIMSampler's ``noise_fn``)."""
+        if timesteps is None:
+            timesteps = self.num_timesteps
+        if start_T is not None:
+            timesteps = min(timesteps, start_T)
+        img, intermediates = self._ancestral_loop(cond, shape, x_T, timesteps, temperature, False, quantize_denoised,
+                                                  mask, x0, log_every_t, callback, img_callback, noise_dropout,
+                                                  score_corrector, corrector_kwargs, noise_fn, q_noise_fn,
+                                                  dropout_fn, cond_noise_fn)
         if return_intermediates:
             return img, intermediates
         return img
@@ -414,20 +515,24 @@ class LatentDiffusion(nn.Module):
         (the reference drops them all)."""
         if shape is None:
             shape = (batch_size, self.channels, self.image_size, self.image_size)
-        if cond is not None:
-            if isinstance(cond, dict):
-                cond = {key: cond[key][:batch_size] if not isinstance(cond[key], list) else
-                        list(map(lambda x: x[:batch_size], cond[key])) for key in cond}
-            else:
-                cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+        cond = self._trim_cond(cond, batch_size)
         if "temperture" in kwargs:
             kwargs.setdefault("temperature", kwargs.pop("temperture"))
-        self._refuse(kwargs.pop("return_codebook_ids", False), kwargs.pop("score_corrector", None),
-                     kwargs.pop("noise_dropout", 0.))
+        self._refuse(kwargs.pop("return_codebook_ids", False))
         extra = {k: kwargs[k] for k in ("temperature", "noise_fn", "q_noise_fn", "callback", "img_callback",
-                                        "start_T", "log_every_t") if k in kwargs}
+                                        "start_T", "log_every_t", "noise_dropout", "score_corrector",
+                                        "corrector_kwargs", "dropout_fn", "cond_noise_fn") if k in kwargs}
         return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose,
                                   timesteps=timesteps, quantize_denoised=quantize_denoised, mask=mask, x0=x0, **extra)
+
+    @torch.no_grad()
+    def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
+        """``ldm/diffusion/ddpm.py:1814-1826``: (samples, intermediates) of the DDIM sampler or of ``sample``."""
+        if ddim:
+            from ..DDIM.ddim import DDIMSampler
+            shape = (self.channels, self.image_size, self.image_size)
+            return DDIMSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
+        return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)
 
     @torch.no_grad()
     def encode_first_stage(self, x):

@@ -31,80 +31,116 @@ int check_launch(const char* what) {
 
 namespace {
 
-__global__ void __launch_bounds__(256) ddim_step_kernel(sdk_ddim_args a) {
-  const int64_t n4 = a.n / 4;
+// e = e_u + g (e_c - e_u)  (ddim.py:178): the two operations of the fused combine and of sdk_cfg_combine
+__device__ __forceinline__ float cfg_combine_elem(float u, float e, float g) {
+  const float d = e - u;
+  return u + g * d;
+}
+
+// keep (0 / 1, one byte per element) times fp32(1 / (1 - p)): the factor F.dropout multiplies by
+__device__ __forceinline__ float dropout_factor(unsigned char keep, float drop_scale) {
+  return (float)keep * drop_scale;
+}
+
+// img = (sa x0 + s1m noise) mask + (1 - mask) img  (ldm/diffusion/ddpm.py:1783-1784), the mask read by
+// index: mask_mode 0 [B,1,H,W], 1 [1,1,H,W], 2 [B,C,H,W]
+__device__ __forceinline__ float masked_q_elem(const sdk_masked_q_args& a, int64_t i, float x0, float nz, float im) {
+  int64_t mi = i;
+  if (a.mask_mode == 0) mi = (i / a.per_sample) * a.hw + i % a.hw;
+  else if (a.mask_mode == 1) mi = i % a.hw;
+  const float mk = a.mask[mi];
+  const float t0 = a.sqrt_acp * x0;
+  const float t1 = a.sqrt_1m_acp * nz;
+  const float q = t0 + t1;
+  const float t2 = q * mk;
+  const float om = 1.f - mk;
+  const float t3 = om * im;
+  return t2 + t3;
+}
+
+// One element of p_sample_ddim (ddim.py:171-204).  e: the model output (ε, or v with v_param); u: the
+// unconditional output (read when e_uncond); p0: pred_x0, an INPUT with pred_x0_in (the quantize_denoised
+// path quantises it between the two halves) and otherwise computed here.  Returns x_prev.
+__device__ __forceinline__ float ddim_elem(const sdk_ddim_ex_args& ex, float x, float e, float u, float nz,
+                                           float kf, float& p0) {
+  const sdk_ddim_args& a = ex.step;
+  if (a.e_uncond) e = cfg_combine_elem(u, e, a.guidance);
+  if (a.v_param) {
+    const float t0 = a.v_sqrt_a * e;
+    const float t1 = a.v_sqrt_1ma * x;
+    e = t0 + t1;
+  }
+  if (!ex.pred_x0_in) {
+    const float t1 = a.sqrt_one_minus_at * e;
+    const float t2 = x - t1;
+    p0 = t2 / a.sqrt_at;
+  }
+  const float dir = a.dir_coef * e;
+  const float t3 = a.sqrt_a_prev * p0;
+  const float t4 = t3 + dir;
+  float nn = (a.sigma * nz) * a.temperature;
+  if (ex.keep) nn = nn * kf;
+  return t4 + nn;
+}
+
+// n4 16-byte groups (0 when a pointer is not aligned for them), then the scalar tail [4 n4, n).  With
+// blend.mask the next iteration's known-region blend (ddim.py:146-147) of x_prev is written to blend.out.
+__global__ void __launch_bounds__(256) ddim_step_kernel(sdk_ddim_ex_args ex, int64_t n4) {
+  const sdk_ddim_args& a = ex.step;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += stride) {
-    f4 x = reinterpret_cast<const f4*>(a.x)[i];
-    f4 e = reinterpret_cast<const f4*>(a.e)[i];
-    if (a.e_uncond) {
-      const f4 u = reinterpret_cast<const f4*>(a.e_uncond)[i];
-      f4 d;
-      for (int j = 0; j < 4; ++j) d[j] = e[j] - u[j];
-      for (int j = 0; j < 4; ++j) e[j] = u[j] + a.guidance * d[j];
-    }
-    if (a.v_param) {
-      for (int j = 0; j < 4; ++j) {
-        const float t0 = a.v_sqrt_a * e[j];
-        const float t1 = a.v_sqrt_1ma * x[j];
-        e[j] = t0 + t1;
-      }
-    }
-    f4 nz = {0.f, 0.f, 0.f, 0.f};
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const bool need_x = !ex.pred_x0_in || a.v_param, blend = ex.blend.mask != nullptr;
+  for (int64_t i = tid; i < n4; i += stride) {
+    const f4 z = {0.f, 0.f, 0.f, 0.f};
+    f4 x = z, u = z, nz = z, p0 = z, kf = z, xp;
+    if (need_x) x = reinterpret_cast<const f4*>(a.x)[i];
+    const f4 e = reinterpret_cast<const f4*>(a.e)[i];
+    if (a.e_uncond) u = reinterpret_cast<const f4*>(a.e_uncond)[i];
     if (a.noise) nz = reinterpret_cast<const f4*>(a.noise)[i];
-    f4 xp, p0;
+    if (ex.pred_x0_in) p0 = reinterpret_cast<const f4*>(a.pred_x0)[i];
+    if (ex.keep) {
+      const uchar4 k = reinterpret_cast<const uchar4*>(ex.keep)[i];
+      kf[0] = dropout_factor(k.x, ex.drop_scale), kf[1] = dropout_factor(k.y, ex.drop_scale);
+      kf[2] = dropout_factor(k.z, ex.drop_scale), kf[3] = dropout_factor(k.w, ex.drop_scale);
+    }
     for (int j = 0; j < 4; ++j) {
-      const float t1 = a.sqrt_one_minus_at * e[j];
-      const float t2 = x[j] - t1;
-      const float pred = t2 / a.sqrt_at;
-      const float dir = a.dir_coef * e[j];
-      const float t3 = a.sqrt_a_prev * pred;
-      const float t4 = t3 + dir;
-      const float nn = (a.sigma * nz[j]) * a.temperature;
-      xp[j] = t4 + nn;
-      p0[j] = pred;
+      float p = p0[j];
+      xp[j] = ddim_elem(ex, x[j], e[j], u[j], nz[j], kf[j], p);
+      p0[j] = p;
     }
     reinterpret_cast<f4*>(a.x_prev)[i] = xp;
-    if (a.pred_x0) reinterpret_cast<f4*>(a.pred_x0)[i] = p0;
+    if (a.pred_x0 && !ex.pred_x0_in) reinterpret_cast<f4*>(a.pred_x0)[i] = p0;
+    if (blend) {
+      const f4 b0 = reinterpret_cast<const f4*>(ex.blend.x0)[i];
+      const f4 bn = reinterpret_cast<const f4*>(ex.blend.noise)[i];
+      f4 o;
+      for (int j = 0; j < 4; ++j) o[j] = masked_q_elem(ex.blend, 4 * i + j, b0[j], bn[j], xp[j]);
+      reinterpret_cast<f4*>(ex.blend.out)[i] = o;
+    }
+  }
+  for (int64_t i = 4 * n4 + tid; i < a.n; i += stride) {
+    float p0 = ex.pred_x0_in ? a.pred_x0[i] : 0.f;
+    const float kf = ex.keep ? dropout_factor(ex.keep[i], ex.drop_scale) : 0.f;
+    const float xp = ddim_elem(ex, need_x ? a.x[i] : 0.f, a.e[i], a.e_uncond ? a.e_uncond[i] : 0.f,
+                               a.noise ? a.noise[i] : 0.f, kf, p0);
+    a.x_prev[i] = xp;
+    if (a.pred_x0 && !ex.pred_x0_in) a.pred_x0[i] = p0;
+    if (blend) ex.blend.out[i] = masked_q_elem(ex.blend, i, ex.blend.x0[i], ex.blend.noise[i], xp);
   }
 }
 
-// Second half of ddim_step_kernel for the quantize_denoised path (DDIM/ddim.py:196-203): pred_x0 is
-// an INPUT here (the caller quantised it in between); e is rebuilt from the same inputs by the same
-// operations, and x_prev by the same operations in the same order, so with the first call's own
-// pred_x0 the result equals that call's x_prev bit for bit.
-__global__ void __launch_bounds__(256) ddim_xprev_kernel(sdk_ddim_args a) {
-  const int64_t n4 = a.n / 4;
+__global__ void __launch_bounds__(256) cfg_combine_kernel(const float* e_u, const float* e_c, float* out, int64_t n,
+                                                          int64_t n4, float g) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += stride) {
-    f4 e = reinterpret_cast<const f4*>(a.e)[i];
-    if (a.e_uncond) {
-      const f4 u = reinterpret_cast<const f4*>(a.e_uncond)[i];
-      f4 d;
-      for (int j = 0; j < 4; ++j) d[j] = e[j] - u[j];
-      for (int j = 0; j < 4; ++j) e[j] = u[j] + a.guidance * d[j];
-    }
-    if (a.v_param) {
-      const f4 x = reinterpret_cast<const f4*>(a.x)[i];
-      for (int j = 0; j < 4; ++j) {
-        const float t0 = a.v_sqrt_a * e[j];
-        const float t1 = a.v_sqrt_1ma * x[j];
-        e[j] = t0 + t1;
-      }
-    }
-    f4 nz = {0.f, 0.f, 0.f, 0.f};
-    if (a.noise) nz = reinterpret_cast<const f4*>(a.noise)[i];
-    const f4 p0 = reinterpret_cast<const f4*>(a.pred_x0)[i];
-    f4 xp;
-    for (int j = 0; j < 4; ++j) {
-      const float dir = a.dir_coef * e[j];
-      const float t3 = a.sqrt_a_prev * p0[j];
-      const float t4 = t3 + dir;
-      const float nn = (a.sigma * nz[j]) * a.temperature;
-      xp[j] = t4 + nn;
-    }
-    reinterpret_cast<f4*>(a.x_prev)[i] = xp;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  for (int64_t i = tid; i < n4; i += stride) {
+    const f4 u = reinterpret_cast<const f4*>(e_u)[i];
+    const f4 c = reinterpret_cast<const f4*>(e_c)[i];
+    f4 o;
+    for (int j = 0; j < 4; ++j) o[j] = cfg_combine_elem(u[j], c[j], g);
+    reinterpret_cast<f4*>(out)[i] = o;
   }
+  for (int64_t i = 4 * n4 + tid; i < n; i += stride) out[i] = cfg_combine_elem(e_u[i], e_c[i], g);
 }
 
 __global__ void __launch_bounds__(256) ddpm_step_kernel(const float* x, const float* eps, const float* noise,
@@ -134,23 +170,28 @@ __device__ __forceinline__ float posterior_recon(const sdk_posterior_args& a, fl
   return xr;
 }
 
-__device__ __forceinline__ float posterior_xprev(const sdk_posterior_args& a, float x, float xr, float nz) {
+// kf: the dropout factor of the noise (ddpm.py:1621-1624: noise*temperature, then F.dropout), read with ex.keep
+__device__ __forceinline__ float posterior_xprev(const sdk_posterior_ex_args& ex, float x, float xr, float nz,
+                                                 float kf) {
+  const sdk_posterior_args& a = ex.step;
   const float t2 = a.coef1 * xr;
   const float t3 = a.coef2 * x;
   const float mean = t2 + t3;
   const float s = a.nonzero * a.sigma;
-  const float nt = nz * a.temperature;
+  float nt = nz * a.temperature;
+  if (ex.keep) nt = nt * kf;
   const float sn = s * nt;
   return mean + sn;
 }
 
 // n4 16-byte groups (0 when a pointer is not 16-byte aligned), then the scalar tail [4 n4, n)
-__global__ void __launch_bounds__(256) posterior_step_kernel(sdk_posterior_args a, int64_t n4) {
+__global__ void __launch_bounds__(256) posterior_step_kernel(sdk_posterior_ex_args ex, int64_t n4) {
+  const sdk_posterior_args& a = ex.step;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const bool need_m = a.stage != 2, need_x = a.stage != 1 || !a.x0_param;
   for (int64_t i = tid; i < n4; i += stride) {
-    f4 x = {0.f, 0.f, 0.f, 0.f}, m = x, nz = x, xr, xp;
+    f4 x = {0.f, 0.f, 0.f, 0.f}, m = x, nz = x, kf = x, xr, xp;
     if (need_x) x = reinterpret_cast<const f4*>(a.x)[i];
     if (need_m) m = reinterpret_cast<const f4*>(a.model_out)[i];
     if (a.stage == 2) xr = reinterpret_cast<const f4*>(a.x_recon_in)[i];
@@ -159,7 +200,12 @@ __global__ void __launch_bounds__(256) posterior_step_kernel(sdk_posterior_args 
     if (a.x_recon) reinterpret_cast<f4*>(a.x_recon)[i] = xr;
     if (a.stage == 1) continue;
     if (a.noise) nz = reinterpret_cast<const f4*>(a.noise)[i];
-    for (int j = 0; j < 4; ++j) xp[j] = posterior_xprev(a, x[j], xr[j], nz[j]);
+    if (ex.keep) {
+      const uchar4 k = reinterpret_cast<const uchar4*>(ex.keep)[i];
+      kf[0] = dropout_factor(k.x, ex.drop_scale), kf[1] = dropout_factor(k.y, ex.drop_scale);
+      kf[2] = dropout_factor(k.z, ex.drop_scale), kf[3] = dropout_factor(k.w, ex.drop_scale);
+    }
+    for (int j = 0; j < 4; ++j) xp[j] = posterior_xprev(ex, x[j], xr[j], nz[j], kf[j]);
     reinterpret_cast<f4*>(a.x_prev)[i] = xp;
   }
   for (int64_t i = 4 * n4 + tid; i < a.n; i += stride) {
@@ -167,24 +213,9 @@ __global__ void __launch_bounds__(256) posterior_step_kernel(sdk_posterior_args 
     const float xr = a.stage == 2 ? a.x_recon_in[i] : posterior_recon(a, x, need_m ? a.model_out[i] : 0.f);
     if (a.x_recon) a.x_recon[i] = xr;
     if (a.stage == 1) continue;
-    a.x_prev[i] = posterior_xprev(a, x, xr, a.noise ? a.noise[i] : 0.f);
+    a.x_prev[i] = posterior_xprev(ex, x, xr, a.noise ? a.noise[i] : 0.f,
+                                  ex.keep ? dropout_factor(ex.keep[i], ex.drop_scale) : 0.f);
   }
-}
-
-// img = (sa x0 + s1m noise) mask + (1 - mask) img  (ldm/diffusion/ddpm.py:1783-1784), the mask read by
-// index: mask_mode 0 [B,1,H,W], 1 [1,1,H,W], 2 [B,C,H,W]
-__device__ __forceinline__ float masked_q_elem(const sdk_masked_q_args& a, int64_t i, float x0, float nz, float im) {
-  int64_t mi = i;
-  if (a.mask_mode == 0) mi = (i / a.per_sample) * a.hw + i % a.hw;
-  else if (a.mask_mode == 1) mi = i % a.hw;
-  const float mk = a.mask[mi];
-  const float t0 = a.sqrt_acp * x0;
-  const float t1 = a.sqrt_1m_acp * nz;
-  const float q = t0 + t1;
-  const float t2 = q * mk;
-  const float om = 1.f - mk;
-  const float t3 = om * im;
-  return t2 + t3;
 }
 
 __global__ void __launch_bounds__(256) masked_q_sample_kernel(sdk_masked_q_args a, int64_t n4) {
@@ -473,23 +504,68 @@ extern "C" int sdk_stochastic_encode(const float* x0, const float* noise, float*
   return check_launch("stochastic_encode");
 }
 
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// the one launch of the DDIM family; the entry points below have checked their own arguments
+static int launch_ddim(const sdk_ddim_ex_args& ex, const char* what, sdk_stream_t stream) {
+  const sdk_ddim_args& a = ex.step;
+  const bool vec = aligned16(a.x) && aligned16(a.e) && aligned16(a.e_uncond) && aligned16(a.noise) &&
+                   aligned16(a.x_prev) && aligned16(a.pred_x0) && aligned16(ex.blend.x0) &&
+                   aligned16(ex.blend.noise) && aligned16(ex.blend.out) &&
+                   (reinterpret_cast<uintptr_t>(ex.keep) & 3) == 0;
+  const int64_t n4 = vec ? a.n / 4 : 0;
+  const int64_t items = std::max<int64_t>(n4, a.n - 4 * n4);
+  const int blocks = (int)std::min<int64_t>((items + 255) / 256, 2048);
+  hipLaunchKernelGGL(ddim_step_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ex, n4);
+  return check_launch(what);
+}
+
+extern "C" int sdk_ddim_step_ex(const sdk_ddim_ex_args* ex, sdk_stream_t stream) {
+  if (!ex) return fail(SDK_EINVAL, "ddim_step_ex: null pointer");
+  const sdk_ddim_args& a = ex->step;
+  const sdk_masked_q_args& m = ex->blend;
+  const bool blend = m.mask != nullptr;
+  if (!a.e || !a.x_prev || (ex->pred_x0_in ? (!a.pred_x0 || (a.v_param && !a.x)) : !a.x))
+    return fail(SDK_EINVAL, "ddim_step_ex: null pointer");
+  if (a.n <= 0) return fail(SDK_EINVAL, "ddim_step_ex: n must be positive");
+  if (ex->keep && !a.noise) return fail(SDK_EINVAL, "ddim_step_ex: keep needs noise");
+  if (blend) {
+    if (!m.x0 || !m.noise || !m.out) return fail(SDK_EINVAL, "ddim_step_ex: blend needs x0, noise and out");
+    if (m.hw <= 0 || m.per_sample <= 0 || m.per_sample % m.hw || a.n % m.per_sample || m.mask_mode < 0 ||
+        m.mask_mode > 2)
+      return fail(SDK_EINVAL, "ddim_step_ex: bad blend geometry (n = batch * per_sample, per_sample = channels * hw)");
+  }
+  return launch_ddim(*ex, "ddim_step_ex", stream);
+}
+
 extern "C" int sdk_ddim_step(const sdk_ddim_args* a, sdk_stream_t stream) {
   if (!a || !a->x || !a->e || !a->x_prev) return fail(SDK_EINVAL, "ddim_step: null pointer");
   if (a->n <= 0 || a->n % 4) return fail(SDK_EINVAL, "ddim_step: n must be a positive multiple of 4");
-  const int64_t n4 = a->n / 4;
-  const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 2048);
-  hipLaunchKernelGGL(ddim_step_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a);
-  return check_launch("ddim_step");
+  sdk_ddim_ex_args ex = {};
+  ex.step = *a;
+  return launch_ddim(ex, "ddim_step", stream);
 }
 
 extern "C" int sdk_ddim_xprev(const sdk_ddim_args* a, sdk_stream_t stream) {
   if (!a || !a->e || !a->x_prev || !a->pred_x0 || (a->v_param && !a->x))
     return fail(SDK_EINVAL, "ddim_xprev: null pointer");
   if (a->n <= 0 || a->n % 4) return fail(SDK_EINVAL, "ddim_xprev: n must be a positive multiple of 4");
-  const int64_t n4 = a->n / 4;
-  const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 2048);
-  hipLaunchKernelGGL(ddim_xprev_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a);
-  return check_launch("ddim_xprev");
+  sdk_ddim_ex_args ex = {};
+  ex.step = *a;
+  ex.pred_x0_in = 1;
+  if (!a->v_param) ex.step.x = nullptr;          // read only for the v conversion
+  return launch_ddim(ex, "ddim_xprev", stream);
+}
+
+extern "C" int sdk_cfg_combine(const float* e_uncond, const float* e_cond, float* out, int64_t n, float guidance,
+                               sdk_stream_t stream) {
+  if (!e_uncond || !e_cond || !out || n <= 0) return fail(SDK_EINVAL, "cfg_combine: bad args");
+  const int64_t n4 = aligned16(e_uncond) && aligned16(e_cond) && aligned16(out) ? n / 4 : 0;
+  const int64_t items = std::max<int64_t>(n4, n - 4 * n4);
+  const int blocks = (int)std::min<int64_t>((items + 255) / 256, 2048);
+  hipLaunchKernelGGL(cfg_combine_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, e_uncond, e_cond, out, n,
+                     n4, guidance);
+  return check_launch("cfg_combine");
 }
 
 extern "C" int sdk_ddpm_step(const float* x, const float* eps, const float* noise, float* out, int64_t n,
@@ -518,23 +594,40 @@ extern "C" int sdk_nchw_to_nhwc(const float* x, void* y, int32_t batch, int32_t 
   return check_launch("nchw_to_nhwc");
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static int posterior_launch(const sdk_posterior_ex_args& ex, const char* what, sdk_stream_t stream);
 
 extern "C" int sdk_posterior_step(const sdk_posterior_args* a, sdk_stream_t stream) {
-  if (!a || a->n <= 0 || a->stage < 0 || a->stage > 2) return fail(SDK_EINVAL, "posterior_step: bad n / stage");
+  if (!a) return fail(SDK_EINVAL, "posterior_step: bad n / stage");
+  sdk_posterior_ex_args ex = {};
+  ex.step = *a;
+  return posterior_launch(ex, "posterior_step", stream);
+}
+
+extern "C" int sdk_posterior_step_ex(const sdk_posterior_ex_args* ex, sdk_stream_t stream) {
+  if (!ex) return fail(SDK_EINVAL, "posterior_step_ex: bad n / stage");
+  if (ex->keep && (ex->step.stage == 1 || !ex->step.noise))
+    return fail(SDK_EINVAL, "posterior_step_ex: keep needs noise and a stage that writes x_prev");
+  return posterior_launch(*ex, "posterior_step_ex", stream);
+}
+
+// the argument checks and the launch shared by the two entry points
+static int posterior_launch(const sdk_posterior_ex_args& ex, const char* what, sdk_stream_t stream) {
+  const sdk_posterior_args* a = &ex.step;
+  const std::string w(what);
+  if (a->n <= 0 || a->stage < 0 || a->stage > 2) return fail(SDK_EINVAL, w + ": bad n / stage");
   const bool need_m = a->stage != 2, need_x = a->stage != 1 || !a->x0_param;
   if ((need_x && !a->x) || (need_m && !a->model_out) || (a->stage == 2 && !a->x_recon_in) ||
       (a->stage != 1 && !a->x_prev) || (a->stage == 1 && !a->x_recon))
-    return fail(SDK_EINVAL, "posterior_step: null pointer");
+    return fail(SDK_EINVAL, w + ": null pointer");
   if (a->stage != 1 && !a->noise && a->nonzero != 0.f)
-    return fail(SDK_EINVAL, "posterior_step: noise may be NULL only where nonzero == 0");
+    return fail(SDK_EINVAL, w + ": noise may be NULL only where nonzero == 0");
   const bool vec = aligned16(a->x) && aligned16(a->model_out) && aligned16(a->noise) && aligned16(a->x_recon_in) &&
-                   aligned16(a->x_prev) && aligned16(a->x_recon);
+                   aligned16(a->x_prev) && aligned16(a->x_recon) && (reinterpret_cast<uintptr_t>(ex.keep) & 3) == 0;
   const int64_t n4 = vec ? a->n / 4 : 0;
   const int64_t items = std::max<int64_t>(n4, a->n - 4 * n4);
   const int blocks = (int)std::min<int64_t>((items + 255) / 256, 2048);
-  hipLaunchKernelGGL(posterior_step_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a, n4);
-  return check_launch("posterior_step");
+  hipLaunchKernelGGL(posterior_step_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ex, n4);
+  return check_launch(what);
 }
 
 extern "C" int sdk_masked_q_sample(const sdk_masked_q_args* a, sdk_stream_t stream) {

@@ -12,10 +12,11 @@ from __future__ import annotations
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (ACT_NONE, ACT_QUICK_GELU, AttentionArgs, XAttnArgs, XAttnLnArgs, FfArgs, TokenLinearArgs, ConvArgs, ConvPlanInfo, DdimArgs, GroupNormArgs,
+from ._lib import (ACT_NONE, ACT_QUICK_GELU, AttentionArgs, XAttnArgs, XAttnLnArgs, FfArgs, TokenLinearArgs, ConvArgs, ConvPlanInfo, GroupNormArgs,
                    OUT_GEGLU_F16, OUT_NCHW_F32, OUT_NHWC_F16, OUT_ROWS_F32, check, lib)
 
 BK = 64          # K tile of the conv kernel (packed weight column padding)
@@ -35,6 +36,15 @@ def _need_cuda(t: torch.Tensor, what: str, dtype=torch.float16):
         raise TypeError(f"sd_amd.{what}: expected a CUDA tensor (HIP path only, no CPU fallback)")
     if dtype is not None and t.dtype != dtype:
         raise TypeError(f"sd_amd.{what}: expected {dtype}, got {t.dtype}")
+
+
+def need_gpu_sampler(option: str, device):
+    """The sampler options added after the plain loops (mask / x0 in DDIM, original steps, ``noise_dropout``,
+    ``score_corrector``, ``progressive_denoising``, ``shorten_cond_schedule``) exist only as HIP kernels: on a
+    model or tensor that is not on the GPU they stay NotImplementedError, raised before any model call."""
+    if torch.device(device).type != "cuda":
+        raise NotImplementedError(f"sd_amd: {option} is implemented on the GPU only (HIP kernels, no CPU "
+                                  f"fallback); got device '{device}'")
 
 
 # --------------------------------------------------------------------------- workspace
@@ -1299,25 +1309,71 @@ def nchw_to_nhwc(x: torch.Tensor, c_pad: int, scale: float = 1.0):
     return y
 
 
-def ddim_step(x, e, sc: dict, noise=None, e_uncond=None, guidance=1.0, v_param=None, x_prev=None, pred_x0=None,
-              temperature=1.0):
-    """Fused DDIM update; ``sc`` holds the fp32 scalars (sampler.DDIMSampler computes them)."""
-    _need_cuda(x, "ddim_step", torch.float32)
-    _need_cuda(e, "ddim_step", torch.float32)
-    x, e = x.contiguous(), e.contiguous()
-    if e_uncond is not None:
-        e_uncond = e_uncond.contiguous()
-    if noise is not None:
-        noise = noise.contiguous()
-    a = DdimArgs()
-    xp = x_prev if x_prev is not None else torch.empty_like(x)
-    p0 = pred_x0 if pred_x0 is not None else torch.empty_like(x)
-    a.x, a.e, a.x_prev, a.pred_x0 = x.data_ptr(), e.data_ptr(), xp.data_ptr(), p0.data_ptr()
+def _drop_scale(what, keep, drop_p, ref, noise):
+    """(keep as a contiguous byte tensor or None, fp32(1 / (1 - p))) of the noise dropout: the factor
+    ``F.dropout`` multiplies the kept elements by; ``p == 1`` multiplies by 0, as torch returns zeros."""
+    p = float(drop_p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"sd_amd.{what}: drop_p must be in [0, 1], got {drop_p}")
+    if keep is None:
+        if p > 0.0:
+            raise ValueError(f"sd_amd.{what}: drop_p > 0 needs keep (one byte per element)")
+        return None, 0.0
+    if not torch.is_tensor(keep) or not keep.is_cuda or keep.device != ref.device or \
+            keep.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"sd_amd.{what}: keep must be a CUDA uint8 / bool tensor on {ref.device}")
+    if keep.shape != ref.shape:
+        raise ValueError(f"sd_amd.{what}: keep {tuple(keep.shape)} vs {tuple(ref.shape)}")
+    if noise is None:
+        raise ValueError(f"sd_amd.{what}: keep needs noise")
+    keep = keep.contiguous()
+    if keep.dtype == torch.bool:
+        keep = keep.view(torch.uint8)
+    return keep, (0.0 if p == 1.0 else float(np.float32(1.0 / (1.0 - p))))
+
+
+def _same_f32(what, ref, **tensors):
+    """Each given tensor: CUDA fp32 of ``ref``'s shape on its device, made contiguous."""
+    out = {}
+    for k, v in tensors.items():
+        if v is None:
+            out[k] = None
+            continue
+        if not torch.is_tensor(v) or not v.is_cuda or v.dtype != torch.float32 or v.device != ref.device:
+            raise ValueError(f"sd_amd.{what}: {k} must be a CUDA fp32 tensor on {ref.device}")
+        if v.shape != ref.shape:
+            raise ValueError(f"sd_amd.{what}: {k} {tuple(v.shape)} vs {tuple(ref.shape)}")
+        out[k] = v.contiguous()
+    return out
+
+
+def _mask_mode(what, mask, shape):
+    """mask_mode of ``sdk_masked_q_sample`` for a mask over an NCHW ``shape``."""
+    if len(shape) != 4:
+        raise ValueError(f"sd_amd.{what}: the mask blend needs NCHW tensors, got {tuple(shape)}")
+    B, Cc, H, W = shape
+    modes = {(B, 1, H, W): 0, (1, 1, H, W): 1, (B, Cc, H, W): 2}      # equal shapes index alike
+    if tuple(mask.shape) not in modes:
+        raise ValueError(f"sd_amd.{what}: mask {tuple(mask.shape)} does not broadcast over {tuple(shape)}")
+    return modes[tuple(mask.shape)]
+
+
+def _ddim_ex(what, ref, x, e, sc, pred_x0_in, noise, e_uncond, guidance, v_param, x_prev, pred_x0, temperature,
+             keep, drop_p, blend_x0, blend_noise, blend_mask, blend_sqrt_acp, blend_sqrt_1m_acp, x_next):
+    """The one call of ``sdk_ddim_step_ex`` behind ``ddim_step`` / ``ddim_xprev``."""
+    t = _same_f32(what, ref, noise=noise, e_uncond=e_uncond)
+    noise, e_uncond = t["noise"], t["e_uncond"]
+    keep, scale = _drop_scale(what, keep, drop_p, ref, noise)
+    ex = _lib.DdimExArgs()
+    a = ex.step
+    a.x = x.data_ptr() if x is not None else None
+    a.e, a.x_prev, a.pred_x0 = e.data_ptr(), x_prev.data_ptr(), pred_x0.data_ptr()
     a.e_uncond = e_uncond.data_ptr() if e_uncond is not None else None
     a.noise = noise.data_ptr() if noise is not None else None
-    a.n = x.numel()
-    a.sqrt_one_minus_at = float(sc["sqrt_one_minus_at"])
-    a.sqrt_at = float(sc["sqrt_at"])
+    a.n = ref.numel()
+    if not pred_x0_in:
+        a.sqrt_one_minus_at = float(sc["sqrt_one_minus_at"])
+        a.sqrt_at = float(sc["sqrt_at"])
     a.dir_coef = float(sc["dir_coef"])
     a.sqrt_a_prev = float(sc["sqrt_a_prev"])
     a.sigma = float(sc["sigma"])
@@ -1326,46 +1382,97 @@ def ddim_step(x, e, sc: dict, noise=None, e_uncond=None, guidance=1.0, v_param=N
     if v_param is not None:
         a.v_param = 1
         a.v_sqrt_a, a.v_sqrt_1ma = float(v_param[0]), float(v_param[1])
-    check(lib().sdk_ddim_step(C.byref(a), _stream()), "ddim_step")
-    return xp, p0
+    ex.pred_x0_in = int(pred_x0_in)
+    if keep is not None:
+        ex.keep, ex.drop_scale = keep.data_ptr(), scale
+    if blend_mask is None:
+        if blend_x0 is not None or blend_noise is not None or x_next is not None:
+            raise ValueError(f"sd_amd.{what}: blend_x0 / blend_noise / x_next need blend_mask")
+        check(lib().sdk_ddim_step_ex(C.byref(ex), _stream()), what)
+        return None
+    if blend_x0 is None or blend_noise is None or blend_sqrt_acp is None or blend_sqrt_1m_acp is None:
+        raise ValueError(f"sd_amd.{what}: the blend needs blend_x0, blend_noise, blend_sqrt_acp and blend_sqrt_1m_acp")
+    t = _same_f32(what, ref, blend_x0=blend_x0, blend_noise=blend_noise)
+    if not torch.is_tensor(blend_mask) or not blend_mask.is_cuda or blend_mask.dtype != torch.float32 or \
+            blend_mask.device != ref.device:
+        raise ValueError(f"sd_amd.{what}: blend_mask must be a CUDA fp32 tensor on {ref.device}")
+    m = ex.blend
+    m.mask_mode = _mask_mode(what, blend_mask, ref.shape)
+    blend_mask = blend_mask.contiguous()
+    if x_next is None:
+        x_next = torch.empty_like(ref)
+    elif x_next.shape != ref.shape or not x_next.is_contiguous() or x_next.dtype != torch.float32 or \
+            x_next.device != ref.device:
+        raise ValueError(f"sd_amd.{what}: x_next must be a contiguous CUDA fp32 tensor of x's shape")
+    m.x0, m.noise, m.mask, m.out = t["blend_x0"].data_ptr(), t["blend_noise"].data_ptr(), blend_mask.data_ptr(), \
+        x_next.data_ptr()
+    m.n, m.per_sample, m.hw = ref.numel(), ref.numel() // ref.shape[0], ref.shape[2] * ref.shape[3]
+    m.sqrt_acp, m.sqrt_1m_acp = float(blend_sqrt_acp), float(blend_sqrt_1m_acp)
+    check(lib().sdk_ddim_step_ex(C.byref(ex), _stream()), what)
+    return x_next
+
+
+def ddim_step(x, e, sc: dict, noise=None, e_uncond=None, guidance=1.0, v_param=None, x_prev=None, pred_x0=None,
+              temperature=1.0, *, keep=None, drop_p=0.0, blend_x0=None, blend_noise=None, blend_mask=None,
+              blend_sqrt_acp=None, blend_sqrt_1m_acp=None, x_next=None):
+    """Fused DDIM update; ``sc`` holds the fp32 scalars (sampler.DDIMSampler computes them).  ``keep`` /
+    ``drop_p``: noise dropout (one byte per element; the noise term is multiplied by keep·fp32(1/(1−p))).
+    ``blend_mask`` (+ ``blend_x0``, ``blend_noise`` and the NEXT timestep's ``blend_sqrt_acp`` /
+    ``blend_sqrt_1m_acp``): the known-region blend of the next loop iteration in the same launch,
+    ``x_next = (sa·x0 + s1m·noise)·mask + (1 − mask)·x_prev``; the return is then (x_prev, pred_x0, x_next)."""
+    _need_cuda(x, "ddim_step", torch.float32)
+    _need_cuda(e, "ddim_step", torch.float32)
+    if e.shape != x.shape:
+        raise ValueError(f"sd_amd.ddim_step: x {tuple(x.shape)} vs e {tuple(e.shape)}")
+    x, e = x.contiguous(), e.contiguous()
+    xp = x_prev if x_prev is not None else torch.empty_like(x)
+    p0 = pred_x0 if pred_x0 is not None else torch.empty_like(x)
+    xn = _ddim_ex("ddim_step", x, x, e, sc, False, noise, e_uncond, guidance, v_param, xp, p0, temperature, keep,
+                  drop_p, blend_x0, blend_noise, blend_mask, blend_sqrt_acp, blend_sqrt_1m_acp, x_next)
+    return (xp, p0) if xn is None else (xp, p0, xn)
 
 
 def ddim_xprev(pred_x0, e, sc: dict, x=None, noise=None, e_uncond=None, guidance=1.0, v_param=None, x_prev=None,
-               temperature=1.0):
+               temperature=1.0, *, keep=None, drop_p=0.0, blend_x0=None, blend_noise=None, blend_mask=None,
+               blend_sqrt_acp=None, blend_sqrt_1m_acp=None, x_next=None):
     """Second half of ``ddim_step`` with ``pred_x0`` as an input (the quantize_denoised path quantises
     it in between): x_prev = sqrt(a_prev)·pred_x0 + dir_coef·e + sigma·noise·temperature, the same
     fp32 operations in the same order.  ``e`` / ``e_uncond`` / ``guidance`` / ``v_param`` are the
-    first call's; ``x`` is needed only with ``v_param``."""
+    first call's; ``x`` is needed only with ``v_param``.  ``keep`` / ``drop_p`` / ``blend_*`` as in
+    ``ddim_step``; with a blend the return is (x_prev, x_next)."""
     _need_cuda(pred_x0, "ddim_xprev", torch.float32)
     _need_cuda(e, "ddim_xprev", torch.float32)
     if e.shape != pred_x0.shape:
         raise ValueError(f"sd_amd.ddim_xprev: pred_x0 {tuple(pred_x0.shape)} vs e {tuple(e.shape)}")
     pred_x0, e = pred_x0.contiguous(), e.contiguous()
-    a = DdimArgs()
     xp = x_prev if x_prev is not None else torch.empty_like(pred_x0)
-    a.e, a.x_prev, a.pred_x0 = e.data_ptr(), xp.data_ptr(), pred_x0.data_ptr()
-    if e_uncond is not None:
-        e_uncond = e_uncond.contiguous()
-        a.e_uncond = e_uncond.data_ptr()
-    if noise is not None:
-        noise = noise.contiguous()
-        a.noise = noise.data_ptr()
-    a.n = pred_x0.numel()
-    a.dir_coef = float(sc["dir_coef"])
-    a.sqrt_a_prev = float(sc["sqrt_a_prev"])
-    a.sigma = float(sc["sigma"])
-    a.temperature = float(temperature)
-    a.guidance = float(guidance)
     if v_param is not None:
         if x is None:
             raise ValueError("sd_amd.ddim_xprev: v_param needs x")
         _need_cuda(x, "ddim_xprev", torch.float32)
         x = x.contiguous()
-        a.x = x.data_ptr()
-        a.v_param = 1
-        a.v_sqrt_a, a.v_sqrt_1ma = float(v_param[0]), float(v_param[1])
-    check(lib().sdk_ddim_xprev(C.byref(a), _stream()), "ddim_xprev")
-    return xp
+    else:
+        x = None
+    xn = _ddim_ex("ddim_xprev", pred_x0, x, e, sc, True, noise, e_uncond, guidance, v_param, xp, pred_x0, temperature,
+                  keep, drop_p, blend_x0, blend_noise, blend_mask, blend_sqrt_acp, blend_sqrt_1m_acp, x_next)
+    return xp if xn is None else (xp, xn)
+
+
+def cfg_combine(e_uncond, e_cond, guidance, out=None):
+    """``e_uncond + guidance·(e_cond − e_uncond)`` (``ddim.py:178``) as a tensor: the two fp32 operations of
+    the combine fused into ``ddim_step``, so ``ddim_step(x, cfg_combine(u, c, g), sc)`` has the bits of
+    ``ddim_step(x, c, sc, e_uncond=u, guidance=g)``."""
+    _need_cuda(e_cond, "cfg_combine", torch.float32)
+    t = _same_f32("cfg_combine", e_cond, e_uncond=e_uncond)
+    if t["e_uncond"] is None:
+        raise ValueError("sd_amd.cfg_combine: e_uncond must be a CUDA fp32 tensor")
+    e_cond = e_cond.contiguous()
+    y = out if out is not None else torch.empty_like(e_cond)
+    if y.shape != e_cond.shape or not y.is_contiguous() or y.dtype != torch.float32 or y.device != e_cond.device:
+        raise ValueError("sd_amd.cfg_combine: out must be a contiguous CUDA fp32 tensor of e_cond's shape")
+    check(lib().sdk_cfg_combine(t["e_uncond"].data_ptr(), e_cond.data_ptr(), y.data_ptr(), e_cond.numel(),
+                                C.c_float(float(guidance)), _stream()), "cfg_combine")
+    return y
 
 
 # --------------------------------------------------------------------------- ancestral sampler / concat
@@ -1409,11 +1516,12 @@ def _t_runs(t, batch):
 
 
 def posterior_step(x, model_out, t, tables: dict, noise=None, *, x0_param=False, clip=False, temperature=1.0,
-                   stage=0, x_recon_in=None, x_prev=None, x_recon=None, want_x_recon=False):
+                   stage=0, x_recon_in=None, x_prev=None, x_recon=None, want_x_recon=False, keep=None, drop_p=0.0):
     """Fused ancestral step of ``LatentDiffusion.p_sample`` (see ``sdk_posterior_step``).  ``t``: a host
     int or one per sample (a launch per run of equal t); ``tables``: host fp32 arrays
     ``c_recip, c_recipm1, coef1, coef2, sigma`` indexed by t.  ``stage`` 0: x_prev (and x_recon when
-    ``want_x_recon``); 1: x_recon only; 2: x_prev from ``x_recon_in``.  Returns (x_prev, x_recon)."""
+    ``want_x_recon``); 1: x_recon only; 2: x_prev from ``x_recon_in``.  ``keep`` / ``drop_p``: noise dropout
+    as in ``ddim_step`` (applied to noise·temperature).  Returns (x_prev, x_recon)."""
     ref = x if x is not None else model_out
     B = ref.shape[0]
     ins = {"x": x, "model_out": model_out, "noise": noise, "x_recon_in": x_recon_in}
@@ -1427,8 +1535,13 @@ def posterior_step(x, model_out, t, tables: dict, noise=None, *, x0_param=False,
         x_prev = torch.empty_like(ref, memory_format=torch.contiguous_format)
     if (stage == 1 or want_x_recon) and x_recon is None:
         x_recon = torch.empty_like(ref, memory_format=torch.contiguous_format)
+    keep, scale = _drop_scale("posterior_step", keep, drop_p, ref, ins["noise"])
+    if keep is not None and stage == 1:
+        raise ValueError("sd_amd.posterior_step: keep needs a stage that writes x_prev")
     per = ref.numel() // B
-    a = _lib.PosteriorArgs()
+    ex = _lib.PosteriorExArgs()
+    ex.drop_scale = scale
+    a = ex.step
     a.stage, a.x0_param, a.clip, a.temperature = int(stage), int(bool(x0_param)), int(bool(clip)), float(temperature)
     for b0, b1, ti in _t_runs(t, B):
         off = b0 * per * 4
@@ -1436,11 +1549,12 @@ def posterior_step(x, model_out, t, tables: dict, noise=None, *, x0_param=False,
             setattr(a, k, v.data_ptr() + off if v is not None else None)
         a.x_prev = x_prev.data_ptr() + off if x_prev is not None and stage != 1 else None
         a.x_recon = x_recon.data_ptr() + off if x_recon is not None else None
+        ex.keep = keep.data_ptr() + b0 * per if keep is not None else None
         a.n = (b1 - b0) * per
         a.c_recip, a.c_recipm1 = float(tables["c_recip"][ti]), float(tables["c_recipm1"][ti])
         a.coef1, a.coef2, a.sigma = float(tables["coef1"][ti]), float(tables["coef2"][ti]), float(tables["sigma"][ti])
         a.nonzero = 0.0 if ti == 0 or noise is None else 1.0      # no noise: x_prev is the posterior mean
-        check(lib().sdk_posterior_step(C.byref(a), _stream()), "posterior_step")
+        check(lib().sdk_posterior_step_ex(C.byref(ex), _stream()), "posterior_step")
     return x_prev, x_recon
 
 
@@ -1453,10 +1567,7 @@ def masked_q_sample(x0, noise, mask, img, t, sqrt_acp, sqrt_1m_acp, out=None):
     if x0.dim() != 4 or noise.shape != x0.shape or img.shape != x0.shape:
         raise ValueError("sd_amd.masked_q_sample: x0, noise and img must be one NCHW shape")
     B, Cc, H, W = x0.shape
-    modes = {(B, 1, H, W): 0, (1, 1, H, W): 1, (B, Cc, H, W): 2}      # equal shapes index alike
-    if tuple(mask.shape) not in modes:
-        raise ValueError(f"sd_amd.masked_q_sample: mask {tuple(mask.shape)} does not broadcast over {tuple(x0.shape)}")
-    mode = modes[tuple(mask.shape)]
+    mode = _mask_mode("masked_q_sample", mask, x0.shape)
     x0, noise, mask = x0.contiguous(), noise.contiguous(), mask.contiguous()
     if not img.is_contiguous():
         if out is img:
