@@ -346,7 +346,8 @@ int sdk_segment_softmax(const float* s, int32_t ld_s, void* p, int32_t ld_p, int
  * BasicTransformerBlock in ONE kernel (GEGLU -> Dropout(0) -> Linear, openai_model/attention.py:129-172,
  * called as x = self.ff(self.norm3(x)) + x at :253); the 4*channels-wide intermediate stays in registers.
  * Shapes: channels == 320 (SD's 64x64-level blocks), features (the GEGLU width, 4*channels in SD) a
- * multiple of 32 (sdk_ff_supported).  t / res / out: [rows, ld] fp16, 16-B aligned, ld % 8 == 0; res may
+ * multiple of 32 (sdk_ff_supported).  t / res / out: [rows, ld] fp16, 16-B aligned, ld % 8 == 0 and
+ * ld >= channels (t_ld, out_ld, and res_ld when res is given; anything else is SDK_EINVAL); res may
  * be NULL or alias out.  Weights go through a one-time pack: w1 fp16 [2*features][channels] (rows
  * [0, features) = a, [features, 2*features) = gate, as nn.Linear(channels, 2*features).weight), b1 fp32
  * [2*features] or NULL, w2 fp16 [channels][features] (nn.Linear(features, channels).weight) ->

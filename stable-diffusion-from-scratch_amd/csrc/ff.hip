@@ -313,7 +313,8 @@ extern "C" int sdk_feed_forward(const sdk_ff_args* a, sdk_stream_t stream) {
   if (!ff_shape_ok(a->channels, a->features))
     return fail(SDK_EINVAL, "feed_forward: channels must be 320, features a multiple of 32");
   if (a->rows <= 0) return fail(SDK_EINVAL, "feed_forward: empty");
-  if (a->t_ld % 8 || a->out_ld % 8 || (a->res && a->res_ld % 8) || a->t_ld < a->channels || a->out_ld < a->channels)
+  if (a->t_ld % 8 || a->out_ld % 8 || (a->res && a->res_ld % 8) || a->t_ld < a->channels || a->out_ld < a->channels ||
+      (a->res && a->res_ld < a->channels))
     return fail(SDK_EINVAL, "feed_forward: row strides must be multiples of 8 and >= channels");
   if (((uintptr_t)a->t | (uintptr_t)a->out | (uintptr_t)a->res | (uintptr_t)a->packed | (uintptr_t)a->b2) & 15)
     return fail(SDK_EINVAL, "feed_forward: pointers must be 16-B aligned");

@@ -105,3 +105,17 @@ def test_feed_forward_rejects(ops, sdk):
     a = _lib.FfArgs()
     a.rows, a.channels, a.features = 128, 640, 2560
     assert _lib.lib().sdk_feed_forward(a, None) != 0
+    # a residual row stride below the channel count is rejected like t_ld / out_ld (the same call with 320 runs)
+    pf = ops.PackedFF(torch.zeros(64, 320).half(), None, torch.zeros(320, 32).half(), None, torch.device(DEV))
+    t = torch.zeros(128, 320, dtype=torch.float16, device=DEV)
+    out, res = torch.empty_like(t), torch.zeros_like(t)
+    a = _lib.FfArgs()
+    a.t, a.res, a.out, a.packed = t.data_ptr(), res.data_ptr(), out.data_ptr(), pf.packed.data_ptr()
+    a.t_ld = a.out_ld = 320
+    a.rows, a.channels, a.features = 128, 320, 32
+    for bad_ld in (312, 0, -320):
+        a.res_ld = bad_ld
+        assert _lib.lib().sdk_feed_forward(a, None) != 0
+    a.res_ld = 320
+    assert _lib.lib().sdk_feed_forward(a, None) == 0
+    torch.cuda.synchronize()
