@@ -510,6 +510,27 @@ typedef struct {
 
 int sdk_concat_nchw_to_nhwc(const sdk_concat_args* a, sdk_stream_t stream);
 
+/* The UNet input of np patches of a large latent, gathered from the full-size tensors (LatentDiffusion.apply_model
+ * with split_input_params, Diffusion/ddpm.py:1151-1266: Unfold of z and of every c_concat entry, then the channel
+ * concat and the input cast): sdk_concat_nchw_to_nhwc applied to the sdk_extract_patches output of every source,
+ * restricted to patches [p0, p0 + np), without any fp32 patch tensor.  nsrc (1..4) NCHW fp32 sources
+ * [batch][channels[i]][h][w] -> y NHWC fp16 [np][kh*kw][c_pad]; patches of kh x kw every (sy, sx), Ly = (h-kh)/sy+1,
+ * Lx = (w-kw)/sx+1, patch index p = l*batch + b with l = ly*Lx + lx (torch.nn.Unfold order); source i lands at
+ * channel offset sum(channels[<i]), channels from the sum up to c_pad are zero.  No scratch.  SDK_EINVAL for a null
+ * pointer, nsrc outside 1..4, kh > h, kw > w, a stride <= 0, c_pad below the channel sum, or a window with p0 < 0,
+ * np < 1 or p0 + np > Ly*Lx*batch. */
+typedef struct {
+  const float* src[4];
+  int32_t channels[4];
+  int32_t nsrc;
+  void* y;
+  int32_t batch, h, w, c_pad;
+  int32_t kh, kw, sy, sx;
+  int32_t p0, np;
+} sdk_patch_pack_args;
+
+int sdk_patch_pack(const sdk_patch_pack_args* a, sdk_stream_t stream);
+
 /* ---------------------------------------------------------------- vector quantiser (vqvae/quantize.py)
  * norms[j] = |codebook[j]|^2 (fp32 fma chain), computed once per codebook [n][d]. */
 int sdk_vq_code_norms(const float* codebook, float* norms, int32_t n, int32_t d, sdk_stream_t stream);

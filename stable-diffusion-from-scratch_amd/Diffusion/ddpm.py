@@ -21,6 +21,13 @@ with torch and multiplied in by ``sdk_posterior_step_ex``), ``progressive_denois
 ``shorten_cond_schedule`` (``make_cond_schedule`` ``:676-681`` and the ``q_sample`` of the conditioning in both
 loops, Gaussian noise) and ``sample_log`` (``:1814-1826``) follow the reference; the hooks ``noise_fn``,
 ``q_noise_fn``, ``dropout_fn`` and ``cond_noise_fn`` supply recorded draws.
+``split_input_params`` (the large-image path) is read in the reference's three places: ``decode_first_stage``
+(``ddpm.py:731``, tiled decode), ``encode_first_stage`` (``:808-846``, tiled encode with ``patch_distributed_vq``; a KL
+posterior is blended as its moments) and ``apply_model`` (``:1151-1266``: the UNet on overlapping
+latent patches gathered by ``sdk_patch_pack`` and blended by ``sdk_fold_patches``, conditioning by key, chunks of
+``max_batch``; ``sp['patch_unet'] = False``, an extension, keeps the UNet untiled).  Refused there: ``return_ids``
+(ValueError, the reference asserts), ``cond_stage_key == 'coordinates_bbox'`` (NotImplementedError) and a patch
+geometry that leaves pixels uncovered (ValueError; the reference divides 0 by 0).
 Refused (NotImplementedError): ``return_codebook_ids`` (the reference itself raises on it), and the four options
 above on a model that is not on the GPU (HIP kernels, no CPU fallback).
 Out of scope (training / Lightning): losses, EMA, optimisers, data, logging.
@@ -67,21 +74,26 @@ class DiffusionWrapper(nn.Module):
                 raise ValueError("sd_amd: timesteps must be integral")
         return t.to(device=device, dtype=torch.long)
 
-    def _unet(self, x, t, context=None, concat=None, y=None):
+    def _unet(self, x, t, context=None, concat=None, y=None, patches=None):
         t = self._int_timesteps(t, x.device)
         kw = {"concat": list(concat)} if concat else {}
         if y is not None:
             kw["y"] = y
+        if patches is not None:
+            kw["patches"] = tuple(int(v) for v in patches)
         if self._graphs_on:
-            return self._graphed(x, t.reshape(-1).expand(x.shape[0]), context, **kw)
+            return self._graphed(x, t.reshape(-1).expand(x.shape[0] if patches is None else kw["patches"][5]),
+                                 context, **kw)
         return self.diffusion_model(x, t, context=context, **kw)
 
-    def forward(self, x, t, c_concat: list = None, c_crossattn: list = None):
+    def forward(self, x, t, c_concat: list = None, c_crossattn: list = None, patches=None):
+        """``patches`` (extension): ``UNetModel.forward``'s patch window; ``x`` and ``c_concat`` are then the
+        full-size tensors, ``t`` and ``c_crossattn`` are per patch."""
         if self.conditioning_key is None:
-            return self._unet(x, t)
+            return self._unet(x, t, patches=patches)
         if self.conditioning_key == "crossattn":
             cc = c_crossattn[0] if len(c_crossattn) == 1 else torch.cat(c_crossattn, 1)
-            return self._unet(x, t, context=cc)
+            return self._unet(x, t, context=cc, patches=patches)
         if self.conditioning_key in ("concat", "hybrid"):
             # Diffusion/ddpm.py:51-63: torch.cat([x] + c_concat, 1) — done inside the UNet's input pack
             if not c_concat:
@@ -91,14 +103,14 @@ class DiffusionWrapper(nn.Module):
                 if not c_crossattn:
                     raise ValueError("sd_amd: conditioning_key=hybrid needs c_crossattn")
                 cc = c_crossattn[0] if len(c_crossattn) == 1 else torch.cat(c_crossattn, 1)
-            return self._unet(x, t, context=cc, concat=c_concat)
+            return self._unet(x, t, context=cc, concat=c_concat, patches=patches)
         if getattr(self.diffusion_model, "num_classes", None) is None:
             raise NotImplementedError(f"sd_amd: conditioning_key={self.conditioning_key} needs a class-conditional "
                                       "UNet (this one has no class head: num_classes is None)")
         # Diffusion/ddpm.py:65-67: the class labels travel as c_crossattn[0]
         if not c_crossattn:
             raise ValueError("sd_amd: conditioning_key=adm needs c_crossattn=[y]")
-        return self._unet(x, t, y=c_crossattn[0])
+        return self._unet(x, t, y=c_crossattn[0], patches=patches)
 
 
 def _is_vq(first_stage):
@@ -212,9 +224,113 @@ class LatentDiffusion(nn.Module):
                 cond = [cond]
             key = "c_concat" if self.model.conditioning_key == "concat" else "c_crossattn"
             cond = {key: cond}
+        sp = getattr(self, "split_input_params", None)
+        if sp is not None and sp.get("patch_unet", True):
+            # Diffusion/ddpm.py:1151: the attribute's presence is the trigger (sp['patch_unet'] = False, an
+            # extension, keeps the UNet untiled); None: the latent is one patch, the untiled call below
+            out = self._apply_model_patched(x_noisy, t, cond, sp, return_ids)
+            if out is not None:
+                return out
         if self.model.conditioning_key is None:
             return self.model(x_noisy, t)
         return self.model(x_noisy, t, **cond)
+
+    # ------------------------------------------------------------------ patch-wise UNet
+    PATCH_CONTEXT_CACHE_SIZE = 4     # repeated conditionings kept: cond, uncond, their CFG concat, one spare
+
+    @staticmethod
+    def _check_coverage(h, w, ks, stride, what):
+        """Patches of ``ks`` every ``stride`` must reach the last row and column and leave no gap between them: a
+        pixel that no patch covers has normalisation 0, and the reference's ``fold(o) / normalization`` is 0 / 0
+        there."""
+        if (h - ks[0]) % stride[0] or (w - ks[1]) % stride[1] or stride[0] > ks[0] or stride[1] > ks[1]:
+            raise ValueError(f"sd_amd: {what} with split_input_params: patches of ks {tuple(ks)} every stride "
+                             f"{tuple(stride)} leave part of the {h}x{w} tensor uncovered ((h - ks) % stride must "
+                             "be 0 and stride <= ks in both dimensions); the blend would be 0 / 0 = NaN there")
+
+    def _patch_weights(self, slot, h, w, Ly, Lx, sp, device):
+        """``get_weighting`` on the device, cached per ``slot`` ('apply' / 'encode') as ``_decode_tiled`` caches
+        its own in ``_tile_w``, so the three tiled paths of one sampling run do not evict each other."""
+        key = (h, w, Ly, Lx, device, sp["clip_min_weight"], sp["clip_max_weight"], bool(sp.get("tie_braker", False)))
+        cache = self.__dict__.setdefault("_patch_w", {})
+        ent = cache.get(slot)
+        if ent is None or ent[0] != key:
+            pix, lw = self.get_weighting(h, w, Ly, Lx, sp)
+            ent = (key, torch.from_numpy(pix).to(device), torch.from_numpy(lw).to(device) if lw is not None else None)
+            cache[slot] = ent
+        return ent[1], ent[2]
+
+    def _patch_contexts(self, c, L, chunk):
+        """``c`` repeated for the L patches (patch ``p = l*B + b`` takes ``c[b]``) and cut into the chunks the UNet
+        is called with, the SAME tensor objects on every call: ``UNetModel._context_kv`` (and a captured graph)
+        recognise a conditioning by identity, so a repeat made afresh per step would re-project K/V for L·B rows at
+        every step.  Keyed on ``(id, _version, L, chunk)`` with a strong reference to ``c``; oldest entry out."""
+        from collections import OrderedDict
+        cache = self.__dict__.setdefault("_patch_ctx", OrderedDict())
+        key = (id(c), c._version, L, chunk)
+        ent = cache.get(key)
+        if ent is None or ent[0] is not c:
+            rep = c.repeat(L, *([1] * (c.dim() - 1)))
+            ent = (c, [rep[i:i + chunk] for i in range(0, rep.shape[0], chunk)])
+            cache[key] = ent
+            while len(cache) > self.PATCH_CONTEXT_CACHE_SIZE:
+                cache.popitem(last=False)
+        cache.move_to_end(key)
+        return ent[1]
+
+    def _apply_model_patched(self, x, t, cond, sp, return_ids):
+        """``Diffusion/ddpm.py:1151-1266``: the UNet on overlapping latent patches of ``ks`` every ``stride``,
+        blended by ``get_weighting``.  The patches are never materialised in fp32: ``UNetModel.forward(patches=)``
+        gathers each chunk of ``sp.get('max_batch', 16)`` patches straight into its input layout
+        (``sdk_patch_pack``), every chunk's output lands in one ``[L, B, C, kh, kw]`` buffer, one
+        ``sdk_fold_patches`` blends it.  Conditioning goes by key: ``c_concat`` entries are spatial and gathered
+        with ``x``, ``c_crossattn`` entries (class labels of 'adm' included) are repeated for the L patches.
+        Returns None when the latent is a single patch."""
+        if return_ids:
+            raise ValueError("sd_amd: return_ids is not supported with split_input_params (Diffusion/ddpm.py:1157)")
+        if self.cond_stage_key == "coordinates_bbox":
+            raise NotImplementedError("sd_amd: split_input_params with cond_stage_key='coordinates_bbox' is not "
+                                      "implemented (the reference has no bbox_tokenizer)")
+        B, _, h, w = x.shape
+        ks, stride, Ly, Lx = ops.patch_grid(h, w, sp["ks"], sp["stride"])
+        self._check_coverage(h, w, ks, stride, "apply_model")
+        L = Ly * Lx
+        if L == 1:
+            return None
+        wrapper = self.model
+        ckey = wrapper.conditioning_key
+        concat = list(cond.get("c_concat") or []) if ckey in ("concat", "hybrid") else []
+        cross = list(cond.get("c_crossattn") or []) if ckey in ("crossattn", "hybrid", "adm") else []
+        for c in concat:
+            if not torch.is_tensor(c) or c.dim() != 4 or c.shape[0] != B or c.shape[2:] != x.shape[2:]:
+                raise ValueError(f"sd_amd: c_concat entries must be NCHW of x's batch and spatial size "
+                                 f"{tuple(x.shape)} to be cut into patches, got {tuple(getattr(c, 'shape', ()))}")
+        chunk = max(1, int(sp.get("max_batch", 16)))
+        total = L * B
+        nchunks = -(-total // chunk)
+        cross = [self._patch_contexts(c if torch.is_tensor(c) else torch.as_tensor(c), L, chunk) for c in cross]
+        unet = wrapper.diffusion_model
+        if cross and ckey != "adm" and 2 * nchunks > unet.CONTEXT_CACHE_SIZE:
+            # K/V of every chunk context of one cond / uncond pair stay resident across the sampler's steps
+            unet.CONTEXT_CACHE_SIZE = 2 * nchunks
+        pix_w, l_w = self._patch_weights("apply", ks[0], ks[1], Ly, Lx, sp, x.device)
+        tt = torch.as_tensor(t).reshape(-1)
+        tt = (tt.expand(B) if tt.numel() == 1 else tt).repeat(L)
+        dtype, x = x.dtype, self._f32(x)
+        buf = None
+        for k, p0 in enumerate(range(0, total, chunk)):
+            n = min(chunk, total - p0)
+            kw = {}
+            if concat:
+                kw["c_concat"] = concat
+            if cross:
+                kw["c_crossattn"] = [c[k] for c in cross]
+            out = wrapper(x, tt[p0:p0 + n], patches=(ks[0], ks[1], stride[0], stride[1], p0, n), **kw)
+            if buf is None:
+                buf = torch.empty(L, B, out.shape[1], ks[0], ks[1], dtype=torch.float32, device=x.device)
+            buf.view(total, out.shape[1], ks[0], ks[1])[p0:p0 + n].copy_(out)
+        out = ops.fold_patches(buf, pix_w, l_w, h, w, stride[0], stride[1], Ly, Lx)
+        return out if dtype == torch.float32 else out.to(dtype)
 
     # ------------------------------------------------------------------ ancestral sampler
     # LatentDiffusion's own sampler (``ldm/diffusion/ddpm.py:1528-1811``; the reference's
@@ -536,12 +652,53 @@ class LatentDiffusion(nn.Module):
 
     @torch.no_grad()
     def encode_first_stage(self, x):
-        """``ldm/diffusion/ddpm.py:1237-1279`` (non-split branch): the first stage's posterior; for a
-        ``VQModelInterface`` the pre-quantisation latent ``h`` of its ``(h, 0, info)`` tuple."""
+        """``ldm/diffusion/ddpm.py:1237-1279``: the first stage's posterior; for a ``VQModelInterface`` the
+        pre-quantisation latent ``h`` of its ``(h, 0, info)`` tuple.  With
+        ``split_input_params['patch_distributed_vq']`` the tiled (patch) encode (``Diffusion/ddpm.py:808-846``)."""
+        sp = getattr(self, "split_input_params", None)
+        if sp and sp.get("patch_distributed_vq"):
+            enc = self._encode_tiled(x, sp)
+            if enc is not None:
+                return enc
         enc = self.first_stage_model.encode(x)
         if _is_vq(self.first_stage_model):
             return enc[0]
         return enc
+
+    def _encode_tiled(self, x, sp):
+        """Patch encode (``Diffusion/ddpm.py:808-846`` + ``get_fold_unfold`` df branch ``:908-919``): image patches
+        of ``ks`` every ``stride`` are encoded in chunks of ``sp.get('max_batch', 16)`` patches·images, weighted and
+        overlap-added at 1 / df (df = vqf) on the device.  A VQ first stage blends its pre-quantisation ``h``; a KL
+        first stage blends the moments (mean | logvar) and returns their ``DiagonalGaussianDistribution`` (the
+        reference stacks distribution objects and cannot run — DESIGN.md Q27).  Returns None for a single tile."""
+        from ..Distribution.distribution import DiagonalGaussianDistribution
+        df = int(sp["vqf"])
+        sp["original_image_size"] = x.shape[-2:]
+        B, _, h, w = x.shape
+        ks, stride, Ly, Lx = ops.patch_grid(h, w, sp["ks"], sp["stride"])
+        if df < 1 or any(v % df for v in ks + stride):
+            raise ValueError(f"sd_amd: encode_first_stage with split_input_params: ks {ks} and stride {stride} must "
+                             f"be divisible by vqf = {df} (the latent patch grid is theirs over vqf)")
+        self._check_coverage(h, w, ks, stride, "encode_first_stage")
+        L = Ly * Lx
+        if L == 1:
+            return None
+        vq = _is_vq(self.first_stage_model)
+        flat = ops.extract_patches(self._f32(x), ks[0], ks[1], stride[0], stride[1]).view(L * B, -1, ks[0], ks[1])
+        chunk = max(1, int(sp.get("max_batch", 16)))
+        enc = []
+        for i in range(0, L * B, chunk):
+            e = self.first_stage_model.encode(flat[i:i + chunk])
+            enc.append(e[0] if vq else e.parameters)
+        enc = torch.cat(enc, 0) if len(enc) > 1 else enc[0]
+        kh, kw = ks[0] // df, ks[1] // df
+        if enc.shape[2:] != (kh, kw):
+            raise ValueError(f"sd_amd: the first stage maps a {ks[0]}x{ks[1]} patch to {tuple(enc.shape[2:])}, "
+                             f"split_input_params['vqf'] = {df} says {kh}x{kw}")
+        pix_w, l_w = self._patch_weights("encode", kh, kw, Ly, Lx, sp, x.device)
+        out = ops.fold_patches(enc.float().view(L, B, enc.shape[1], kh, kw), pix_w, l_w, h // df, w // df,
+                               stride[0] // df, stride[1] // df, Ly, Lx)
+        return out if vq else DiagonalGaussianDistribution(out)
 
     def get_first_stage_encoding(self, encoder_posterior, noise=None):
         """``ldm/diffusion/ddpm.py:795-806``: scale_factor * posterior sample (fused on the device)."""

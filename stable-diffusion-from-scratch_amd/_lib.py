@@ -111,6 +111,12 @@ class ConcatArgs(C.Structure):
                 ("c_pad", i32)]
 
 
+class PatchPackArgs(C.Structure):
+    _fields_ = [("src", vp * 4), ("channels", i32 * 4), ("nsrc", i32), ("y", vp), ("batch", i32), ("h", i32),
+                ("w", i32), ("c_pad", i32), ("kh", i32), ("kw", i32), ("sy", i32), ("sx", i32), ("p0", i32),
+                ("np", i32)]
+
+
 class Resize2dArgs(C.Structure):
     _fields_ = [("x", vp), ("y", vp), ("planes", i32), ("h", i32), ("w", i32), ("out_h", i32), ("out_w", i32),
                 ("mode", i32), ("scale_h", C.c_double), ("scale_w", C.c_double)]
@@ -125,7 +131,7 @@ GN_STATS = ("given", "slice", "chunked", "parts")              # SDK_GN_STATS_*
 GN_APPLY = ("none", "in_stats", "flat", "row", "stride")       # SDK_GN_APPLY_*
 
 EXPORTS = ["sdk_conv2d_plan", "sdk_conv2d", "sdk_group_norm_workspace", "sdk_group_norm_affine", "sdk_group_norm_apply", "sdk_group_norm_apply_padded", "sdk_group_norm_apply_ex", "sdk_group_norm", "sdk_group_norm_finalize", "sdk_group_norm_plan", "sdk_layer_norm",
-           "sdk_attention", "sdk_attention_form", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_ddim_step_ex", "sdk_cfg_combine", "sdk_posterior_step", "sdk_posterior_step_ex", "sdk_masked_q_sample", "sdk_concat_nchw_to_nhwc", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
+           "sdk_attention", "sdk_attention_form", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_ddim_step_ex", "sdk_cfg_combine", "sdk_posterior_step", "sdk_posterior_step_ex", "sdk_masked_q_sample", "sdk_concat_nchw_to_nhwc", "sdk_patch_pack", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
            "sdk_diag_gaussian_sample", "sdk_stochastic_encode", "sdk_token_embedding", "sdk_extract_patches",
            "sdk_fold_patches", "sdk_vq_code_norms", "sdk_vq_nearest_splits", "sdk_vq_nearest", "sdk_vq_lookup", "sdk_vq_remap",
            "sdk_upsample_bilinear2x", "sdk_upsample_nearest2x_padded", "sdk_zero_border", "sdk_gelu",
@@ -192,6 +198,7 @@ def lib():
     L.sdk_posterior_step_ex.argtypes = [C.POINTER(PosteriorExArgs), vp]
     L.sdk_masked_q_sample.argtypes = [C.POINTER(MaskedQArgs), vp]
     L.sdk_concat_nchw_to_nhwc.argtypes = [C.POINTER(ConcatArgs), vp]
+    L.sdk_patch_pack.argtypes = [C.POINTER(PatchPackArgs), vp]
     L.sdk_vq_code_norms.argtypes = [vp, vp, i32, i32, vp]
     L.sdk_vq_nearest_splits.argtypes = [i64, i32, i32]
     L.sdk_vq_nearest_splits.restype = i32

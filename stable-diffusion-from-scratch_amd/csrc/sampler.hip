@@ -232,12 +232,14 @@ __global__ void __launch_bounds__(256) masked_q_sample_kernel(sdk_masked_q_args 
   for (int64_t i = 4 * n4 + tid; i < a.n; i += stride) a.out[i] = masked_q_elem(a, i, a.x0[i], a.noise[i], a.img[i]);
 }
 
-// channel c of the concat of the sources at (b, pix); zero from the channel sum up to c_pad
-__device__ __forceinline__ float concat_fetch(const sdk_concat_args& a, int64_t b, int64_t pix, int c) {
+// channel c of the concat of the sources (planes of hw floats) at (b, pix); zero from the channel sum up to
+// c_pad.  Args: sdk_concat_args or sdk_patch_pack_args (the same src / channels / nsrc)
+template <class Args>
+__device__ __forceinline__ float concat_fetch(const Args& a, int64_t hw, int64_t b, int64_t pix, int c) {
 #pragma unroll
   for (int s = 0; s < 4; ++s) {   // constant trip count: src[] / channels[] stay in scalar registers
     if (s >= a.nsrc) break;
-    if (c < a.channels[s]) return a.src[s][(b * a.channels[s] + c) * a.hw + pix];
+    if (c < a.channels[s]) return a.src[s][(b * a.channels[s] + c) * hw + pix];
     c -= a.channels[s];
   }
   return 0.f;
@@ -255,14 +257,55 @@ __global__ void __launch_bounds__(256) concat_nchw_to_nhwc_kernel(sdk_concat_arg
     const int g = (int)(e / bhw);
     const int64_t r = e - g * bhw, b = r / a.hw, pix = r - b * a.hw;
     h8 o;
-    for (int j = 0; j < 8; ++j) o[j] = (half_t)concat_fetch(a, b, pix, 8 * g + j);
+    for (int j = 0; j < 8; ++j) o[j] = (half_t)concat_fetch(a, a.hw, b, pix, 8 * g + j);
     *reinterpret_cast<h8*>(y + r * a.c_pad + 8 * g) = o;
   }
   const int c0 = 8 * ngrp;
   for (int64_t e = tid; e < nscal; e += stride) {
     const int c = c0 + (int)(e / bhw);
     const int64_t r = e % bhw, b = r / a.hw, pix = r - b * a.hw;
-    y[r * a.c_pad + c] = (half_t)concat_fetch(a, b, pix, c);
+    y[r * a.c_pad + c] = (half_t)concat_fetch(a, a.hw, b, pix, c);
+  }
+}
+
+// row r of the patch window -> (image b, offset of its pixel in an h x w plane): r = (pl*kh + i)*kw + j, patch
+// p = p0 + pl = l*batch + b, l = ly*Lx + lx (torch.nn.Unfold order, as extract_patches_kernel)
+__device__ __forceinline__ void patch_row(const sdk_patch_pack_args& a, int Lx, int64_t r, int64_t& b, int64_t& pix) {
+  const int khw = a.kh * a.kw;
+  const int64_t p = a.p0 + r / khw;
+  const int q = (int)(r % khw), i = q / a.kw, j = q - i * a.kw;
+  const int64_t l = p / a.batch;
+  b = p - l * a.batch;
+  const int ly = (int)(l / Lx), lx = (int)(l - (int64_t)ly * Lx);
+  pix = (int64_t)(ly * a.sy + i) * a.w + lx * a.sx + j;
+}
+
+// concat_nchw_to_nhwc_kernel over the rows of np patches gathered from the full-size sources: items
+// [0, nvec) one 8-channel group of one patch pixel (a 16-byte store; consecutive lanes take consecutive
+// pixels of one patch row, so the reads are runs of kw floats), items [nvec, nvec + nscal) one channel
+// past the last full group
+__global__ void __launch_bounds__(256) patch_pack_kernel(sdk_patch_pack_args a, int Lx, int ngrp, int64_t nvec,
+                                                         int64_t nscal) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t rows = (int64_t)a.np * a.kh * a.kw, hw = (int64_t)a.h * a.w;
+  half_t* y = reinterpret_cast<half_t*>(a.y);
+  for (int64_t e = tid; e < nvec; e += stride) {
+    const int g = (int)(e / rows);
+    const int64_t r = e - g * rows;
+    int64_t b, pix;
+    patch_row(a, Lx, r, b, pix);
+    h8 o;
+    for (int j = 0; j < 8; ++j) o[j] = (half_t)concat_fetch(a, hw, b, pix, 8 * g + j);
+    *reinterpret_cast<h8*>(y + r * a.c_pad + 8 * g) = o;
+  }
+  const int c0 = 8 * ngrp;
+  for (int64_t e = tid; e < nscal; e += stride) {
+    const int c = c0 + (int)(e / rows);
+    const int64_t r = e % rows;
+    int64_t b, pix;
+    patch_row(a, Lx, r, b, pix);
+    y[r * a.c_pad + c] = (half_t)concat_fetch(a, hw, b, pix, c);
   }
 }
 
@@ -659,6 +702,30 @@ extern "C" int sdk_concat_nchw_to_nhwc(const sdk_concat_args* a, sdk_stream_t st
   hipLaunchKernelGGL(concat_nchw_to_nhwc_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a, ngrp, nvec,
                      nscal);
   return check_launch("concat_nchw_to_nhwc");
+}
+
+extern "C" int sdk_patch_pack(const sdk_patch_pack_args* a, sdk_stream_t stream) {
+  if (!a || !a->y || a->nsrc < 1 || a->nsrc > 4 || a->batch <= 0 || a->h <= 0 || a->w <= 0)
+    return fail(SDK_EINVAL, "patch_pack: bad args (1..4 sources)");
+  int64_t csum = 0;
+  for (int s = 0; s < a->nsrc; ++s) {
+    if (!a->src[s] || a->channels[s] <= 0) return fail(SDK_EINVAL, "patch_pack: null source / channels <= 0");
+    csum += a->channels[s];
+  }
+  if (a->c_pad < csum) return fail(SDK_EINVAL, "patch_pack: c_pad below the channel sum");
+  if (a->kh <= 0 || a->kw <= 0 || a->sy <= 0 || a->sx <= 0 || a->kh > a->h || a->kw > a->w)
+    return fail(SDK_EINVAL, "patch_pack: bad geometry (0 < kh <= h, 0 < kw <= w, strides > 0)");
+  const int Ly = (a->h - a->kh) / a->sy + 1, Lx = (a->w - a->kw) / a->sx + 1;
+  const int64_t total = (int64_t)Ly * Lx * a->batch;
+  if (a->p0 < 0 || a->np < 1 || (int64_t)a->p0 + a->np > total)
+    return fail(SDK_EINVAL, "patch_pack: patch window [p0, p0 + np) outside the " + std::to_string(total) +
+                                " patches");
+  const int ngrp = (a->c_pad % 8 == 0 && aligned16(a->y)) ? a->c_pad / 8 : 0;
+  const int64_t rows = (int64_t)a->np * a->kh * a->kw;
+  const int64_t nvec = ngrp * rows, nscal = (a->c_pad - 8 * ngrp) * rows;
+  const int blocks = (int)std::min<int64_t>((std::max(nvec, nscal) + 255) / 256, 2048);
+  hipLaunchKernelGGL(patch_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a, Lx, ngrp, nvec, nscal);
+  return check_launch("patch_pack");
 }
 
 extern "C" const char* sdk_last_error(void) { return g_last_error.c_str(); }

@@ -44,10 +44,10 @@ class GraphedUNet:
         self._gen = getattr(unet, "prepare_generation", None)
 
     @staticmethod
-    def _key(x, timesteps, context, concat=(), y=None):
+    def _key(x, timesteps, context, concat=(), y=None, patches=None):
         ctx = None if context is None else (id(context), tuple(context.shape), context.dtype)
         return (tuple(x.shape), x.dtype, tuple(timesteps.shape), ctx, tuple(tuple(c.shape) for c in concat),
-                None if y is None else tuple(y.shape))
+                None if y is None else tuple(y.shape), None if patches is None else tuple(patches))
 
     def _valid(self, ent, context):
         if context is None:
@@ -55,7 +55,7 @@ class GraphedUNet:
         return ent["ctx"] is context and ent["ctx_version"] == context._version
 
     @torch.no_grad()
-    def __call__(self, x, timesteps, context=None, concat=None, y=None):
+    def __call__(self, x, timesteps, context=None, concat=None, y=None, patches=None):
         # concat tensors (UNetModel.forward's extension) are inputs like x: shapes in the key, contents
         # copied into static fp32 buffers on every replay (no identity cache, they change per call)
         concat = [] if concat is None else [c.to(device=x.device, dtype=torch.float32) for c in concat]
@@ -63,12 +63,15 @@ class GraphedUNet:
         # (a device y is never range-checked on the host: an id out of range gives NaN rows, not a fault)
         if y is not None:
             y = torch.as_tensor(y).to(device=x.device, dtype=torch.int64)
-        kw = lambda cc, yy=None: dict({"concat": cc} if cc else {}, **({} if yy is None else {"y": yy}))  # noqa: E731
+        # a patch window (UNetModel.forward's ``patches``) is baked into the captured pack kernel's arguments: it
+        # is part of the key, so a graph is never replayed for another window
+        pk = {} if patches is None else {"patches": tuple(int(v) for v in patches)}
+        kw = lambda cc, yy=None: dict({"concat": cc} if cc else {}, **({} if yy is None else {"y": yy}), **pk)  # noqa: E731
         gen = getattr(self.unet, "prepare_generation", None)
         if gen != self._gen:
             self.reset()
             self._gen = gen
-        key = self._key(x, timesteps, context, concat, y)
+        key = self._key(x, timesteps, context, concat, y, pk.get("patches"))
         ent = self.graphs.get(key)
         if ent is not None and not self._valid(ent, context):
             del self.graphs[key]

@@ -414,17 +414,27 @@ class UNetModel(nn.Module):
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
-    def forward(self, x, timesteps=None, context=None, y=None, concat=None, **kwargs):
+    def forward(self, x, timesteps=None, context=None, y=None, concat=None, patches=None, **kwargs):
         """``concat`` (extension, not in the reference's signature): a list of up to three NCHW tensors
         whose channels follow ``x``'s, i.e. the result of ``forward(torch.cat([x] + concat, 1), ...)``
         (``DiffusionWrapper.forward`` 'concat' / 'hybrid', ``Diffusion/ddpm.py:51-63``) with the concat
-        folded into the NCHW → NHWC pack of the input, so the concatenated tensor is never built."""
+        folded into the NCHW → NHWC pack of the input, so the concatenated tensor is never built.
+
+        ``patches`` (extension): ``(kh, kw, sy, sx, p0, np)`` — ``x`` and ``concat`` are the full-size tensors and
+        the UNet runs on their patches ``[p0, p0 + np)`` of ``kh x kw`` every ``(sy, sx)`` (Unfold order,
+        ``p = l*B + b``), gathered by ``ops.patch_pack`` in place of the input pack; ``timesteps``, ``y`` and
+        ``context`` are per patch (batch ``np``).  Returns the patches' output ``[np, C, kh, kw]``, the layout
+        ``ops.fold_patches`` takes once the windows are laid end to end (``LatentDiffusion.apply_model`` with
+        ``split_input_params``)."""
+        if patches is not None:
+            kh, kw, sy, sx, p0, npatch = (int(v) for v in patches)
+        B = x.shape[0] if patches is None else npatch
         assert (y is not None) == (self.num_classes is not None), \
             "must specify y if and only if the model is class-conditional"
         if y is not None:
             if not torch.is_tensor(y):
                 y = torch.as_tensor(y)
-            assert y.shape == (x.shape[0],), f"y must have shape ({x.shape[0]},), got {tuple(y.shape)}"
+            assert y.shape == (B,), f"y must have shape ({B},), got {tuple(y.shape)}"
             if not y.is_cuda:
                 # a host tensor is checked here; a device y is not synced (the kernel writes NaN rows instead)
                 if y.numel() and (int(y.min()) < 0 or int(y.max()) >= self.num_classes):
@@ -446,7 +456,6 @@ class UNetModel(nn.Module):
             raise TypeError("sd_amd.UNetModel: HIP path only — move inputs to the GPU")
         if self._prepared_on != x.device:
             self.prepare(x.device)
-        B = x.shape[0]
         t = timesteps
         if not torch.is_tensor(t):
             t = torch.tensor(t)
@@ -466,7 +475,10 @@ class UNetModel(nn.Module):
         emb_all = ops.linear(self._pc_emb, emb, silu=True, out_mode=ops.OUT_ROWS_F32)
         kv, Lc = self._context_kv(context)
         st = {"emb": emb_all, "kv": kv, "Lc": Lc}
-        if concat:
+        if patches is not None:
+            h = ops.patch_pack([x.float()] + [c.to(device=x.device, dtype=torch.float32) for c in concat],
+                               self._cin_pad, kh, kw, sy, sx, p0, npatch)
+        elif concat:
             h = ops.concat_nchw_to_nhwc([x.float()] + [c.to(device=x.device, dtype=torch.float32) for c in concat],
                                         self._cin_pad)
         else:

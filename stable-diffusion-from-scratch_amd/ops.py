@@ -1502,6 +1502,53 @@ def concat_nchw_to_nhwc(srcs, c_pad: int):
     return y
 
 
+def patch_grid(h: int, w: int, ks, stride):
+    """Patch geometry of ``split_input_params`` on an ``h x w`` tensor: ``(ks', stride', Ly, Lx)`` with ``ks`` and
+    ``stride`` clipped to the tensor (``Diffusion/ddpm.py:818-825``) and ``Ly x Lx`` the ``torch.nn.Unfold`` patch
+    grid.  Host arithmetic only."""
+    h, w = int(h), int(w)
+    ks, stride = (int(ks[0]), int(ks[1])), (int(stride[0]), int(stride[1]))
+    if h <= 0 or w <= 0 or min(ks) <= 0 or min(stride) <= 0:
+        raise ValueError(f"sd_amd.patch_grid: sizes must be positive, got {h}x{w}, ks {ks}, stride {stride}")
+    ks = (min(ks[0], h), min(ks[1], w))
+    stride = (min(stride[0], h), min(stride[1], w))
+    return ks, stride, (h - ks[0]) // stride[0] + 1, (w - ks[1]) // stride[1] + 1
+
+
+def patch_pack(srcs, c_pad: int, kh: int, kw: int, sy: int, sx: int, p0: int = 0, np: int = None):
+    """``concat_nchw_to_nhwc`` of the ``extract_patches`` output of every source, for the patches
+    ``[p0, p0 + np)`` (``np=None``: up to the last one), in one pass without any fp32 patch tensor: 1..4 NCHW fp32
+    sources of one ``B, H, W`` → NHWC fp16 ``[np, kh, kw, c_pad]``; patch ``p = l*B + b`` (Unfold order)."""
+    srcs = list(srcs)
+    if not 1 <= len(srcs) <= 4:
+        raise ValueError(f"sd_amd.patch_pack: 1..4 sources, got {len(srcs)}")
+    for s in srcs:
+        _need_cuda(s, "patch_pack", torch.float32)
+        if s.dim() != 4 or s.shape[0] != srcs[0].shape[0] or s.shape[2:] != srcs[0].shape[2:]:
+            raise ValueError("sd_amd.patch_pack: sources must be NCHW with the same batch and spatial size, got "
+                             f"{[tuple(t.shape) for t in srcs]}")
+    srcs = [s.contiguous() for s in srcs]
+    B, _, H, W = srcs[0].shape
+    csum = sum(s.shape[1] for s in srcs)
+    if c_pad < csum:
+        raise ValueError(f"sd_amd.patch_pack: c_pad {c_pad} below the channel sum {csum}")
+    if not (0 < kh <= H and 0 < kw <= W and sy > 0 and sx > 0):
+        raise ValueError(f"sd_amd.patch_pack: patches {kh}x{kw} every ({sy}, {sx}) do not fit {H}x{W}")
+    total = ((H - kh) // sy + 1) * ((W - kw) // sx + 1) * B
+    if np is None:
+        np = total - p0
+    if p0 < 0 or np < 1 or p0 + np > total:
+        raise ValueError(f"sd_amd.patch_pack: window [{p0}, {p0 + np}) outside the {total} patches")
+    y = torch.empty(np, kh, kw, c_pad, dtype=torch.float16, device=srcs[0].device)
+    a = _lib.PatchPackArgs()
+    for i, s in enumerate(srcs):
+        a.src[i], a.channels[i] = s.data_ptr(), s.shape[1]
+    a.nsrc, a.y, a.batch, a.h, a.w, a.c_pad = len(srcs), y.data_ptr(), B, H, W, c_pad
+    a.kh, a.kw, a.sy, a.sx, a.p0, a.np = kh, kw, sy, sx, p0, np
+    check(lib().sdk_patch_pack(C.byref(a), _stream()), "patch_pack")
+    return y
+
+
 def _t_runs(t, batch):
     """``t`` (an int, or one int per sample) → [(first sample, end sample, t)] runs of equal t."""
     ts = [int(t)] * batch if not isinstance(t, (list, tuple)) else [int(v) for v in t]
