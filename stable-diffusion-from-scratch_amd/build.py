@@ -10,21 +10,28 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsdk_amd.so")
-SOURCES = ["conv.hip", "norm.hip", "attention.hip", "sampler.hip", "xattn.hip", "ff.hip", "token.hip", "vq.hip", "cond.hip",
-           "probe.hip"]
-# conv.hip is compiled once per part (its SDK_CONV_PART partition: host planner + small kernels, then the tile
-# kernel instantiations in four groups) so the objects build in parallel
-CONV_PARTS = 6
+SOURCES = ["norm.hip", "attention.hip", "sampler.hip", "xattn.hip", "ff.hip", "token.hip", "vq.hip", "cond.hip", "probe.hip"]
+# the conv units: the host planner, the small kernels, and the tile kernels, whose one small source is compiled
+# once per part (-DSDK_CONV_PART=k expands the launcher of that part's variant rows) so the objects build in parallel
+CONV_TILE_PARTS = 5
 
 
 def _units():
     """(source, object stem, extra defines) per compiled object."""
+    yield "conv_plan.hip", "conv_plan", []
+    yield "conv_small.hip", "conv_small", []
+    for k in range(1, CONV_TILE_PARTS + 1):
+        yield "conv_tile.hip", f"conv_tile_p{k}", [f"-DSDK_CONV_PART={k}"]
     for src in SOURCES:
-        if src == "conv.hip":
-            for k in range(CONV_PARTS):
-                yield src, f"conv_p{k}", [f"-DSDK_CONV_PART={k}"]
-        else:
-            yield src, src.replace(".hip", ""), []
+        yield src, src.replace(".hip", ""), []
+
+
+def _deps(src: str, csrc: str):
+    """The files an object of ``src`` is rebuilt for: every conv unit depends on every conv*.h of ``csrc``."""
+    headers = [os.path.join(csrc, "common.h"), os.path.join(HERE, "..", "include", "sdk_amd.h")]
+    if src.startswith("conv"):
+        headers += sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.startswith("conv") and f.endswith(".h"))
+    return [os.path.join(csrc, src)] + headers
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result"]
 # attention: IEEE mode off + no NaN semantics, so fmaxf on MFMA results is one v_max3 instead of
@@ -75,7 +82,6 @@ def build(force: bool = False, verbose: bool = False, diag: bool = False, tag: s
     for k, v in (extra or {}).items():
         extra_flags[k] = extra_flags.get(k, []) + list(v)
     os.makedirs(bdir, exist_ok=True)
-    headers = [os.path.join(csrc, "common.h"), os.path.join(HERE, "..", "include", "sdk_amd.h")]
     jobs = []
     objs = []
     for src, stem, udefs in _units():
@@ -86,7 +92,7 @@ def build(force: bool = False, verbose: bool = False, diag: bool = False, tag: s
         dflags = (["-DSDK_CONV_DIAGNOSTICS"] if diag else []) + list(defines) + udefs
         fl = " ".join(FLAGS + extra_flags.get(src, []) + dflags)
         stale_flags = not os.path.exists(flags_file) or open(flags_file).read() != fl
-        if force or stale_flags or _needs(o, [s] + headers) or not os.path.exists(o + ".res"):
+        if force or stale_flags or _needs(o, _deps(src, csrc)) or not os.path.exists(o + ".res"):
             # the sidecar is rewritten only after this object compiled (run() below): an interrupted
             # or failed compile leaves no object that claims the new flags
             for stale in (o, flags_file):

@@ -1,460 +1,11 @@
-// Implicit-GEMM convolution / GEMM for gfx950 (MI355X), fp16 in, fp32 accumulate on MFMA.
-//
-// One kernel covers every conv and Linear of the UNet and the VAE decoder:
-//   out[m, n] = sum_k A[m, k] * W[n, k] + epilogue
-// m = output pixel (b, oy, ox) of an NHWC tensor, k = (segment, tap, channel).
-//
-// Tile: 128(M) x 128(N) x 64(K), 256 threads = 4 waves in 2x2, each wave a
-// 64x64 sub-tile = 2x2 v_mfma_f32_32x32x16_f16.  A and W tiles are staged
-// global -> registers -> LDS (double buffer, one barrier per K step); the
-// register stage is where the A prologue runs: channel-concat source select,
-// nearest-x2 upsample indexing, GroupNorm affine + SiLU and zero padding.  The
-// next tile's global loads are issued before the current tile's MFMAs and
-// written to LDS after them (issue-early / write-late).  LDS rows are 128 B,
-// XOR-swizzled on the 16-B chunk index with (row>>1)&7 so the MFMA fragment
-// reads (ds_read_b128, 16 distinct rows per lane group) are conflict-free.
-// The epilogue adds bias and the per-(batch, channel) timestep-embedding
-// broadcast in registers, optionally pairs (x, gate) columns for GEGLU,
-// stages the fp16 tile through LDS and writes it with 16-B coalesced stores
-// fused with the residual add.  Low-parallelism shapes (the 16x16 / 8x8 UNet
-// levels) split K across workgroups into fp32 slabs reduced by a second kernel.
-#include <algorithm>
-#include <string>
-#include <type_traits>
-#include <cstdio>
-#include <cstdlib>
-
-#include "common.h"
-
-#ifndef SDK_CONV_PART
-#define SDK_CONV_PART -1
-#endif
-#define SDK_PART(k) (SDK_CONV_PART < 0 || SDK_CONV_PART == (k))
+// The conv tile kernels: the LDS-DMA conv_glds_kernel and the phased conv_ph_kernel, their epilogues and their
+// launchers.  conv_tile.hip includes this once per compile part and instantiates that part's kernels only.
+#pragma once
+#include "conv_cfg.h"
+#include "conv_device.h"
 
 namespace sdk {
 namespace {
-
-constexpr int BM = 128, BN = 128, BK = 64, NT = 256;
-constexpr int TILE_H = BM * BK;          // halfs per A (or B) tile
-constexpr int CT_LD = BN + 8;            // epilogue LDS row stride (halfs)
-
-struct Seg {
-  const half_t* src0;
-  const half_t* src1;
-  const float* gscale;
-  const float* gshift;
-  int c_split, cin, cin_pad, ld0, ld1;
-  int h, w, ksize, stride, pad, upsample, silu;
-  int k_off;            // first packed-K column of this segment
-  int tiles_per_tap;    // cin_pad / BK
-  int kt_begin;         // first global K tile of this segment
-};
-
-struct Params {
-  Seg seg[2];
-  int nseg, kt_total;
-  int M, N, Npad, batch, ho, wo, hw_out;
-  const half_t* W;
-  int ldw, wrows;       // packed weight rows (>= N); reads beyond are clamped
-  long long wbs;        // per-image weights: W of image b at W + b * wbs (0: one W); LDS-DMA kernels only
-  const float* bias;
-  const float* row_bias;
-  int rb_ld;
-  const half_t* res;
-  int res_ld;
-  void* out;
-  int out_ld, out_mode;
-  float* partial;       // split-K slabs [split][M][Npad]
-  int split, kt_per_split;
-  int tiles_m, tiles_n;
-  int variant;          // 0: register-staged 128x128 (A transforms); 2/3/4: LDS-DMA 256x256 / 256x128 / 128x128
-  int act;              // epilogue activation after bias / embedding, before the residual (sdk_conv_act);
-                        // only the register-staged kernel and the split-K reduce apply it (act forces
-                        // variant 0), so the LDS-DMA kernels' epilogues carry no activation code
-  int nomask;           // segment 0 has every tap in range (pad 0, no pad_end / upsample, cin % 64 == 0):
-                        // the LDS-DMA A gather is a lane base + a scalar tap offset, no masks
-  float2* gnp;          // GroupNorm statistics of the fp16 output: [batch][gn_nch][N] (mean, M2) over
-  int gn_nch;           // hw_out / gn_nch rows each (one chunk = one M-tile, or 64 rows of the split-K reduce)
-  // in-launch split-K (LDS-DMA tile kernels, split == 2): the K halves of a tile combine inside the launch;
-  // partial = one fp32 accumulator blob per (tile, half), tcnt = per-tile arrival counters (left zero)
-  int inl;
-  unsigned* tcnt;
-  int gm;               // unsplit plans: tiles visited in groups of gm M-panels, N-tile major inside a group
-  unsigned long long* stamps;   // diagnostics build only: 8 shader-clock stamps per workgroup, or null
-  int stamps_rt;                // diagnostics: slots 6 / 7 = s_memrealtime at entry / end (SDK_CONV_STAMPS=2)
-  int simple;           // token GEMM (one segment, 1x1 stride 1, no masks, one source): linear A / W K offsets
-  // phase form of nearest-x2 + 3x3 (sdk_conv_args.upsample_phase): four 2x2 convs over the zero-bordered low-res
-  // image, one per output parity (a, b).  GEMM rows are phase major, each phase's ph_rows = batch * hw_out rows
-  // padded to ph_rows_pad (a multiple of the M-tile, so no tile straddles two phases' weights): row
-  // m = phase * ph_rows_pad + (img * ho + i) * wo + j gathers the 2x2 window at (i + a, j + b) and stores to
-  // output pixel (img, 2i + a, 2j + b); ho / wo / hw_out are the LOW-RES extents, M = 4 * ph_rows_pad
-  int phase, ph_rows, ph_rows_pad;
-};
-
-// Phase form: output row (pixel index of the 2ho x 2wo NHWC output) of GEMM row m, or -1 for a padding row
-__device__ __forceinline__ int phase_out_row(const Params& p, int m) {
-  const int ph = m / p.ph_rows_pad, rp = m - ph * p.ph_rows_pad;
-  if (ph > 3 || rp >= p.ph_rows) return -1;
-  const int img = rp / p.hw_out, rem = rp - img * p.hw_out;
-  const int i = rem / p.wo, j = rem - i * p.wo;
-  return (img * 2 * p.ho + 2 * i + (ph >> 1)) * (2 * p.wo) + 2 * j + (ph & 1);
-}
-
-// the output row an epilogue stores GEMM row m to (-1: none).  PH: compiled with the phase form (only the
-// linear-issue conv_glds_kernel and the split-K reduces; everything else keeps its code)
-template <bool PH>
-__device__ __forceinline__ int out_row(const Params& p, int m) {
-  if (PH && p.phase) return phase_out_row(p, m);
-  return m < p.M ? m : -1;
-}
-
-// diagnostics build: s_memtime at kernel entry / after the prologue / after the K loop / at the end (+ after
-// epilogue groups 0-3 at 4-7), by
-// thread 0 of every workgroup (sdk_diag_conv_stamps copies them out); compiled out of the product library
-// SDK_CONV_STAMPS=2: slots 6 / 7 hold s_memrealtime (100 MHz) at entry / end instead of epilogue groups 2 / 3, so the
-// shader clock the workgroup ran at is (memtime end - entry) / (realtime end - entry) x 100 MHz (MI355X_MICROARCH.md
-// 'DVFS give-back' item 6)
-__device__ __forceinline__ void ph_stamp(const Params& p, int i) {
-#ifdef SDK_CONV_DIAGNOSTICS
-  if (p.stamps && threadIdx.x == 0) {
-    const size_t wg = ((size_t)blockIdx.x + (size_t)blockIdx.y * gridDim.x) * 8;
-    if (p.stamps_rt && i >= 6) return;
-    p.stamps[wg + i] = __builtin_amdgcn_s_memtime();
-    if (p.stamps_rt && (i == 0 || i == 3)) p.stamps[wg + (i == 0 ? 6 : 7)] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
-}
-
-// epilogue activation (CLIP's quick_gelu x*sigmoid(1.702x), transformers activations.py QuickGELUActivation)
-__device__ __forceinline__ float act_fn(int act, float x) {
-  if (act == SDK_ACT_QUICK_GELU) return x * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * x));
-  return x;
-}
-
-__device__ __forceinline__ int swz(int row, int chunk) {   // element offset inside a [128][64] tile
-  return row * BK + ((chunk ^ ((row >> 1) & 7)) << 3);
-}
-
-__device__ __forceinline__ h8 ldg16(const half_t* p) { return *reinterpret_cast<const h8*>(p); }
-
-// fp16 output row stores of the epilogues (SDK_STORE_HINT=1: non-temporal; 2: no store — A/B builds only)
-__device__ __forceinline__ void st_out16(half_t* p, const h8& v) {
-#if defined(SDK_STORE_HINT) && SDK_STORE_HINT == 1
-  __builtin_nontemporal_store(v, reinterpret_cast<h8*>(p));
-#elif defined(SDK_STORE_HINT) && SDK_STORE_HINT == 2
-  asm volatile("" ::"v"(v), "v"(p));   // A/B build only: the whole epilogue but its global stores
-#else
-  *reinterpret_cast<h8*>(p) = v;
-#endif
-}
-
-// A-row context: per thread 4 rows (r = (tid>>3) + 32*i), fixed over the K loop.
-struct RowCtx {
-  int b[4], oy[4], ox[4];
-  bool valid[4];
-};
-
-__device__ __forceinline__ void load_a(const Params& p, const RowCtx& rc, int kt, int chunk, h8 (&va)[4],
-                                       bool (&ok)[4], int& cglob, int& segi) {
-  segi = (p.nseg > 1 && kt >= p.seg[1].kt_begin) ? 1 : 0;
-  const Seg& s = p.seg[segi];
-  const int local = kt - s.kt_begin, taps = s.ksize * s.ksize;
-  const int cblk = local / taps, tap = local - cblk * taps;   // K order: channel block, then tap
-  const int c = cblk * BK + chunk * 8;
-  const int ky = tap / s.ksize, kx = tap - ky * s.ksize;
-  cglob = c;
-  const bool cok = c < s.cin;
-  const half_t* base;
-  int ld, cc;
-  if (c < s.c_split) { base = s.src0; ld = s.ld0; cc = c; }
-  else { base = s.src1; ld = s.ld1; cc = c - s.c_split; }
-  const int lh = s.upsample ? 2 * s.h : s.h, lw = s.upsample ? 2 * s.w : s.w;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int iy = rc.oy[i] * s.stride - s.pad + ky;
-    int ix = rc.ox[i] * s.stride - s.pad + kx;
-    bool in = rc.valid[i] && cok && iy >= 0 && iy < lh && ix >= 0 && ix < lw;
-    ok[i] = in;
-    if (s.upsample) { iy >>= 1; ix >>= 1; }
-    h8 v = {};
-    if (in) v = ldg16(base + ((size_t)((size_t)rc.b[i] * s.h + iy) * s.w + ix) * ld + cc);
-    va[i] = v;
-  }
-}
-
-// GroupNorm affine + SiLU on the staged registers; zero after the transform
-// (the conv pads the *normalised* activation).
-__device__ __forceinline__ void transform_a(const Params& p, const RowCtx& rc, int segi, int c, h8 (&va)[4],
-                                            const bool (&ok)[4]) {
-  const Seg& s = p.seg[segi];
-  if (s.gscale == nullptr && !s.silu) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (!ok[i]) va[i] = h8{};
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    h8 v = va[i];
-    if (ok[i]) {
-      float sc[8], sh[8];
-      if (s.gscale) {
-        const f4* ps = reinterpret_cast<const f4*>(s.gscale + (size_t)rc.b[i] * s.cin + c);
-        const f4* pt = reinterpret_cast<const f4*>(s.gshift + (size_t)rc.b[i] * s.cin + c);
-        f4 s0 = ps[0], s1 = ps[1], t0 = pt[0], t1 = pt[1];
-        sc[0] = s0[0]; sc[1] = s0[1]; sc[2] = s0[2]; sc[3] = s0[3];
-        sc[4] = s1[0]; sc[5] = s1[1]; sc[6] = s1[2]; sc[7] = s1[3];
-        sh[0] = t0[0]; sh[1] = t0[1]; sh[2] = t0[2]; sh[3] = t0[3];
-        sh[4] = t1[0]; sh[5] = t1[1]; sh[6] = t1[2]; sh[7] = t1[3];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { sc[j] = 1.f; sh[j] = 0.f; }
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float x = (float)v[j] * sc[j] + sh[j];
-        if (s.silu) x = x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-        v[j] = (half_t)x;
-      }
-    } else {
-      v = h8{};
-    }
-    va[i] = v;
-  }
-}
-
-
-// ---------------------------------------------------------------------- shared epilogue
-// acc[i][j] (32x32 MFMA tile) element r of lane (fr = lane&31, fh = lane>>5):
-//   row = m_w + i*32 + (r&3) + 8*(r>>2) + 4*fh, col = n_w + j*32 + fr   (block-local)
-// LDS `smem` must be free (all waves past their last LDS read) on entry.
-template <int FM, int FN, int TBM, int TBN, int TNT>
-__device__ __forceinline__ void epilogue(const Params& p, f16v (&acc)[FM][FN], half_t* smem, int m0, int n0, int m_w,
-                                         int n_w, int split_idx) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int fr = lane & 31, fh = lane >> 5;
-  constexpr int CLD = TBN + 8;
-  if (p.split > 1) {
-    float* slab = p.partial + (size_t)split_idx * p.M * p.Npad;
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int m = m0 + m_w + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-          const int n = n0 + n_w + j * 32 + fr;
-          if (m < p.M) slab[(size_t)m * p.Npad + n] = acc[i][j][r];
-        }
-    return;
-  }
-  const int mode = p.out_mode;
-  if (mode == SDK_OUT_GEGLU_F16) {
-    // weight rows of each 64-wide column pair: [x (32) | gate (32)] -> output col = (n_w + j*32)/2 + fr
-    static_assert(FN % 2 == 0, "GEGLU needs an even number of 32-col tiles per wave");
-#pragma unroll
-    for (int jp = 0; jp < FN / 2; ++jp) {
-      const int nx = n0 + n_w + jp * 64 + fr, ng = nx + 32;
-      const float bx = (p.bias && nx < p.N) ? p.bias[nx] : 0.f, bg = (p.bias && ng < p.N) ? p.bias[ng] : 0.f;
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int rl = m_w + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-          const float x = acc[i][2 * jp][r] + bx, g = acc[i][2 * jp + 1][r] + bg;
-          smem[rl * CLD + n_w / 2 + jp * 32 + fr] = (half_t)(x * gelu_erf(g));
-        }
-    }
-    __syncthreads();
-    constexpr int OW = TBN / 2;
-    const int ncol0 = n0 / 2;
-    half_t* out = reinterpret_cast<half_t*>(p.out);
-    for (int e = tid; e < TBM * (OW / 8); e += TNT) {
-      const int rl = e / (OW / 8), c8 = (e - rl * (OW / 8)) * 8;
-      const int m = m0 + rl, n = ncol0 + c8;
-      if (m >= p.M || n >= p.N / 2) continue;
-      h8 v = *reinterpret_cast<const h8*>(smem + rl * CLD + c8);
-      if (p.res) {
-        h8 rr = ldg16(p.res + (size_t)m * p.res_ld + n);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = (half_t)((float)v[q] + (float)rr[q]);
-      }
-      st_out16(out + (size_t)m * p.out_ld + n, v);
-    }
-    return;
-  }
-  float bn[FN];
-#pragma unroll
-  for (int j = 0; j < FN; ++j) {
-    const int n = n0 + n_w + j * 32 + fr;
-    bn[j] = (p.bias && n < p.N) ? p.bias[n] : 0.f;
-  }
-  if (mode == SDK_OUT_NHWC_F16) {
-    const bool uniform_b = (p.hw_out % 32) == 0;
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-      const int mblk = m0 + m_w + i * 32;
-      const int bidx = min(mblk, p.M - 1) / p.hw_out;
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const int n = n0 + n_w + j * 32 + fr;
-        float add = bn[j];
-        if (p.row_bias && n < p.N && uniform_b) add += p.row_bias[(size_t)bidx * p.rb_ld + n];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int rl = m_w + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-          float v = acc[i][j][r] + add;
-          if (p.row_bias && n < p.N && !uniform_b) {
-            const int m = min(m0 + rl, p.M - 1);
-            v += p.row_bias[(size_t)(m / p.hw_out) * p.rb_ld + n];
-          }
-          smem[rl * CLD + n_w + j * 32 + fr] = (half_t)act_fn(p.act, v);
-        }
-      }
-    }
-    __syncthreads();
-    half_t* out = reinterpret_cast<half_t*>(p.out);
-    for (int e = tid; e < TBM * (TBN / 8); e += TNT) {
-      const int rl = e / (TBN / 8), c8 = (e - rl * (TBN / 8)) * 8;
-      const int m = m0 + rl, n = n0 + c8;
-      if (m >= p.M || n >= p.N) continue;
-      h8 v = *reinterpret_cast<const h8*>(smem + rl * CLD + c8);
-      if (p.res) {
-        h8 rr = ldg16(p.res + (size_t)m * p.res_ld + n);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = (half_t)((float)v[q] + (float)rr[q]);
-      }
-      st_out16(out + (size_t)m * p.out_ld + n, v);
-    }
-    return;
-  }
-  // fp32 outputs (small: time-embedding projections, final 4/3-channel convs)
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-      const int n = n0 + n_w + j * 32 + fr;
-      if (n >= p.N) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + m_w + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-        if (m >= p.M) continue;
-        const int b = m / p.hw_out;
-        float v = acc[i][j][r] + bn[j];
-        if (p.row_bias) v += p.row_bias[(size_t)b * p.rb_ld + n];
-        v = act_fn(p.act, v);
-        if (p.res) v += (float)p.res[(size_t)m * p.res_ld + n];
-        float* out = reinterpret_cast<float*>(p.out);
-        if (mode == SDK_OUT_NCHW_F32)
-          out[((size_t)b * p.N + n) * p.hw_out + (m - b * p.hw_out)] = v;
-        else
-          out[(size_t)m * p.out_ld + n] = v;
-      }
-    }
-}
-
-#if SDK_PART(0)   // the register-staged kernel: host planner part only
-__global__ void __launch_bounds__(NT, 2) conv_igemm_kernel(Params p) {
-  __shared__ __attribute__((aligned(16))) half_t smem[4 * TILE_H];   // A0 A1 B0 B1 = 64 KiB
-  half_t* As = smem;
-  half_t* Bs = smem + 2 * TILE_H;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int ntiles = p.tiles_m * p.tiles_n;
-  const int tile = xcd_remap(blockIdx.x, ntiles);
-  const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int kt0 = blockIdx.y * p.kt_per_split;
-  const int kt1 = min(p.kt_total, kt0 + p.kt_per_split);
-
-  const int lrow = tid >> 3, chunk = tid & 7;
-  RowCtx rc;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int m = m0 + lrow + 32 * i;
-    rc.valid[i] = m < p.M;
-    int mm = rc.valid[i] ? m : 0;
-    int b = mm / p.hw_out, rem = mm - b * p.hw_out;
-    int oy = rem / p.wo;
-    rc.b[i] = b; rc.oy[i] = oy; rc.ox[i] = rem - oy * p.wo;
-  }
-  const half_t* wrow[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) wrow[i] = p.W + (size_t)min(n0 + lrow + 32 * i, p.wrows - 1) * p.ldw + chunk * 8;
-
-  f16v acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = f16v{};
-
-  h8 va[4], vb[4];
-  bool ok[4];
-  int cglob = 0, segi = 0;
-
-  auto load_b = [&](int kt) {
-    const int si = (p.nseg > 1 && kt >= p.seg[1].kt_begin) ? 1 : 0;
-    const int kcol = p.seg[si].k_off + (kt - p.seg[si].kt_begin) * BK;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) vb[i] = ldg16(wrow[i] + kcol);
-  };
-  auto store_tiles = [&](int buf) {
-    half_t* a = As + buf * TILE_H;
-    half_t* bsh = Bs + buf * TILE_H;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = lrow + 32 * i;
-      *reinterpret_cast<h8*>(a + swz(r, chunk)) = va[i];
-      *reinterpret_cast<h8*>(bsh + swz(r, chunk)) = vb[i];
-    }
-  };
-
-  if (kt0 < kt1) {
-    load_a(p, rc, kt0, chunk, va, ok, cglob, segi);
-    load_b(kt0);
-    transform_a(p, rc, segi, cglob, va, ok);
-    store_tiles(0);
-  }
-  __syncthreads();
-
-  const int fr = lane & 31, fh = lane >> 5;
-  for (int kt = kt0; kt < kt1; ++kt) {
-    const int cur = (kt - kt0) & 1;
-    const bool more = kt + 1 < kt1;
-    if (more) {
-      load_a(p, rc, kt + 1, chunk, va, ok, cglob, segi);
-      load_b(kt + 1);
-    }
-    const half_t* a = As + cur * TILE_H;
-    const half_t* bsh = Bs + cur * TILE_H;
-#pragma unroll
-    for (int kk = 0; kk < BK / 16; ++kk) {
-      h8 fa[2], fb[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        fa[t] = *reinterpret_cast<const h8*>(a + swz(wm * 64 + t * 32 + fr, kk * 2 + fh));
-        fb[t] = *reinterpret_cast<const h8*>(bsh + swz(wn * 64 + t * 32 + fr, kk * 2 + fh));
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
-    if (more) {
-      transform_a(p, rc, segi, cglob, va, ok);
-      store_tiles(cur ^ 1);
-    }
-    __syncthreads();
-  }
-
-  const int m_w = wm * 64, n_w = wn * 64;
-  epilogue<2, 2, BM, BN, NT>(p, acc, smem, m0, n0, m_w, n_w, blockIdx.y);
-}
-#endif  // SDK_PART(0)
-
-
 
 // ---------------------------------------------------------------------- direct epilogue
 // Transposed accumulator (D^T = W A^T): lane (fr = lane&31, fh = lane>>5) owns output
@@ -587,8 +138,6 @@ __device__ __forceinline__ void epilogue_direct(const Params& p, f16v (&acc)[FM]
 // chunks and issues coalesced 16-B stores (+ 16-B residual loads): 64-128 contiguous
 // bytes per pixel row per instruction.  Wave-private scratch: no barrier, LDS ops of one
 // wave complete in order.
-constexpr int EPI_RS = 72;                 // scratch row stride (halfs) = 144 B
-constexpr int EPI_BYTES = 32 * EPI_RS * 2;  // per-wave scratch
 
 // ---------------------------------------------------------------------- GroupNorm statistics in the epilogue
 // The convs that produce a GroupNorm input (ResBlock conv1 / conv2, Down/Upsample, proj_out, conv_in)
@@ -670,26 +219,6 @@ __device__ __forceinline__ void gn_tile_store(const Params& p, int m0, int n0, F
     chunk = ph * (p.hw_out / TBM) + (rp - b0 * p.hw_out) / TBM;
   }
   p.gnp[((size_t)b0 * p.gn_nch + chunk) * p.N + n0 + t] = r;
-}
-
-// split-K reduce: a lane's pivot-shifted sums over its rows (registers are plentiful there)
-struct GnAcc {
-  float piv[8], s1[8], s2[8];
-};
-
-__device__ __forceinline__ void gn_acc_add(GnAcc& a, const h8& v, bool first) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float x = (float)v[j];
-    if (first) {
-      a.piv[j] = x;
-      a.s1[j] = 0.f;
-      a.s2[j] = 0.f;
-    }
-    const float d = x - a.piv[j];
-    a.s1[j] += d;
-    a.s2[j] = fmaf(d, d, a.s2[j]);
-  }
 }
 
 // Bias and the timestep-embedding row (row_bias of the tile's image) are staged in LDS once per
@@ -1080,29 +609,6 @@ __device__ __forceinline__ void epilogue16_tile_direct(const Params& p, f4 (&acc
 // would drain it).  No VGPR staging, no A-side transform (GroupNorm+SiLU is
 // applied by gn_apply before 3x3 convs); every segment must be transform-free.
 __device__ __attribute__((aligned(16))) half_t g_zero_page[8];
-
-template <int BM_, int BN_, int WM_, int WN_, int NS_ = 2, bool M16_ = false, int OCC_ = 1>
-struct Cfg {
-  static constexpr int TBM = BM_, TBN = BN_, WM = WM_, WN = WN_;
-  static constexpr int NS = NS_;                         // LDS ring stages (NS - 1 K-steps of DMA in flight)
-  static constexpr bool M16 = M16_;                      // v_mfma_f32_16x16x32_f16 instead of 32x32x16
-  static constexpr int OCC = OCC_;                       // workgroups meant to share a CU (LDS and VGPR budget)
-  static constexpr int NW = WM * WN, NT = NW * 64;
-  static constexpr int TM = TBM / WM, TN = TBN / WN;
-  static constexpr int FM = TM / 32, FN = TN / 32;
-  static constexpr int FM16 = TM / 16, FN16 = TN / 16;
-  static constexpr int ROWS = TBM + TBN;                 // LDS rows (128 B) per stage
-  static constexpr int STAGE_H = ROWS * BK;              // halfs per stage
-  static constexpr int NINSTR = ROWS / 8;                // 1-KiB DMA pieces per stage
-  static constexpr int GPW = (NINSTR + NW - 1) / NW;     // pieces per wave (padded: the same count in
-                                                         // every wave keeps the vmcnt immediate exact)
-  static_assert(TBM % 8 == 0 && TBN % 8 == 0, "A/B boundary must align to an 8-row piece");
-  static constexpr int RING_BYTES = NS * STAGE_H * 2 + (GPW * NW > NINSTR ? 1024 : 0);  // + dummy slot
-  static constexpr int LDS_BYTES = RING_BYTES + 2 * TBN * 4;   // + staged bias / embedding row
-  static_assert(LDS_BYTES * OCC <= 160 * 1024, "OCC rings must fit the 160 KiB LDS");
-  static_assert(RING_BYTES / NW >= EPI_BYTES + TM / 16 * TN * 8, "per-wave epilogue scratch + parked GN statistics");
-  static_assert(TBN <= NT, "one staged bias element per thread");
-};
 
 #define SDK_SEGF(f) (s1 ? p.seg[1].f : p.seg[0].f)
 
@@ -1496,7 +1002,7 @@ __global__ void __launch_bounds__(CF::NT, CF::OCC * CF::NW / 4) conv_glds_kernel
   // A/B builds only (-DSDK_ABL_DMA=1 / 2 / 3, wrong outputs by design): the K loop issues no A / W / A and W
   // pieces after the prologue — the ablations that say which operand's fill bounds the loop
 #if defined(SDK_ABL_DMA)
-#define SDK_ABL_DMA_SKIP(IS_A) (((SDK_ABL_DMA) & 1) && (IS_A)) || (((SDK_ABL_DMA) & 2) && !(IS_A))
+#define SDK_ABL_DMA_SKIP(IS_A) ((((SDK_ABL_DMA) & 1) && (IS_A)) || (((SDK_ABL_DMA) & 2) && !(IS_A)))
 #else
 #define SDK_ABL_DMA_SKIP(IS_A) false
 #endif
@@ -1798,38 +1304,6 @@ __global__ void __launch_bounds__(CF::NT, CF::OCC * CF::NW / 4) conv_glds_kernel
   ph_stamp(p, 3);
 }
 
-using Cfg256x256 = Cfg<256, 256, 2, 4>;
-using Cfg256x128 = Cfg<256, 128, 4, 2>;
-using Cfg128x128 = Cfg<128, 128, 2, 2>;
-// N = 320 / 640 / 960 levels of SD: 32x160 wave tiles (5 MFMA tiles per wave)
-using Cfg256x160 = Cfg<256, 160, 8, 1>;
-using Cfg128x320 = Cfg<128, 320, 4, 2>;
-// deeper rings for tiles whose K-step is shorter than the DMA latency (~1 us issue -> landed):
-// 128x128 (512 MFMA cycles per K-step per CU) and 256x128 / 128x256 (1024)
-using Cfg128x128r4 = Cfg<128, 128, 2, 2, 4>;   // 128 KiB
-using Cfg128x128r3 = Cfg<128, 128, 2, 2, 3>;   // 96 KiB
-using Cfg256x128r3 = Cfg<256, 128, 4, 2, 3>;   // 144 KiB
-using Cfg128x256r3 = Cfg<128, 256, 2, 4, 3>;   // 144 KiB
-// the same tiles on v_mfma_f32_16x16x32_f16 (on random data the 16x16 shape holds a higher clock
-// under load than 32x32 at equal cycles per FLOP: MI355X_MICROARCH.md 'DVFS give-back' (7))
-using Cfg256x320m = Cfg<256, 320, 8, 2, 2, true>;
-using Cfg128x320m = Cfg<128, 320, 4, 2, 2, true>;
-using Cfg256x160m = Cfg<256, 160, 8, 1, 2, true>;
-using Cfg128x256r3m = Cfg<128, 256, 2, 4, 3, true>;
-using Cfg128x128r3m = Cfg<128, 128, 2, 2, 3, true>;
-// short-K token GEMMs (K = 320-1280): two workgroups per CU, so one's epilogue (store drain) runs
-// under the other's K loop — a 2-stage 128x160 / 128x128 ring is 74 / 65 KiB
-using Cfg128x160o2m = Cfg<128, 160, 4, 1, 2, true, 2>;
-using Cfg128x128o2m = Cfg<128, 128, 2, 2, 2, true, 2>;
-using Cfg128x160r4m = Cfg<128, 160, 4, 1, 4, true>;      // one workgroup, 3 K-steps of DMA in flight
-// 8-wave 256-row tiles with 64-row (256x320) / 128-row (256x256) wave tiles at two waves per SIMD (256 VGPRs): half
-// the LDS fragment reads per MFMA of the 16-wave 256x320 (each B fragment feeds 4 or 8 MFMAs instead of 2) and room
-// for the fragment reads of the next group to be in flight under the current one's MFMAs (round-6 ablation, profiles/
-// r6_conv_ablation.txt: the 16-wave 256x320 runs at 1.16 PF/s with no DMA at all — its LDS-read -> MFMA chain, not
-// the fill, bounds it)
-using Cfg256x320w8m = Cfg<256, 320, 4, 2, 2, true>;
-using Cfg256x256w8m = Cfg<256, 256, 2, 4, 2, true>;
-
 // ---------------------------------------------------------------------- 16x16x32 epilogues
 // Transposed 16x16 accumulator (D^T = W A^T, v_mfma_f32_16x16x32_f16): lane l holds pixel
 // m = m_w + 16*i + (l & 15) and the 4 consecutive channels n = n_w + 32*b + 16*j + 4*(l >> 4) + q.
@@ -1989,14 +1463,6 @@ __device__ __forceinline__ void epilogue16_direct(const Params& p, f4 (&acc)[4][
 // the same vmcnt immediates.  A wave owns pixels {a*128 + wr*64 + (0..63)} and
 // channels {64*wc + 32*b + (0..31)}, so a GEGLU (x, gate) 32-channel pair sits in one
 // wave (W0 / W1 halves) and the direct epilogue applies unchanged.
-template <int S_, int D_>
-struct PhCfg {
-  static constexpr int S = S_, D = D_;
-  static constexpr int RING_BYTES = S * 128 * BK * 2;
-  static constexpr bool VEC = RING_BYTES + 2 * 256 * 4 <= 160 * 1024;   // room for the staged bias / embedding
-  static constexpr int LDS_BYTES = RING_BYTES + (VEC ? 2 * 256 * 4 : 0);
-  static_assert(S >= D + 2 && D >= 2 && RING_BYTES <= 160 * 1024, "ring too small / too large");
-};
 constexpr int PH_HALF = 128 * BK;   // halfs per half-tile slot
 
 // SIMPLE (p.simple, DBG == 0): the linear A issue of conv_glds_kernel — per-lane row offsets fixed, the K step's
@@ -2279,9 +1745,6 @@ __global__ void __launch_bounds__(512) conv_ph_kernel(Params p) {
   }
 }
 
-using PhCfg8 = PhCfg<8, 6>;
-using PhCfg10 = PhCfg<10, 8>;
-
 template <class PC, int DBG = 0, bool M16 = false>
 int launch_ph(const Params& p, hipStream_t s) {
   static std::atomic<unsigned long long> attr_set{0}, attr_simple{0};
@@ -2299,392 +1762,6 @@ int launch_ph(const Params& p, hipStream_t s) {
                      PC::LDS_BYTES, s, p);
   return check_launch("conv_ph");
 }
-
-#if SDK_PART(0)   // split-K reduces, direct and skinny kernels: host planner part only
-// Split-K reduction + epilogue: 8 columns per thread.
-// Slab sum of one (row, 8-column) octet: the slabs' 32-B pieces are loaded SK_U splits at a time
-// (independent loads in flight, instead of one dependent round trip per split) and added in split
-// order — a clamped slab past the end is loaded and selected away, never branched around (hipcc
-// would sink a conditional load under its branch and wait for each) — so the sum equals a plain loop's.
-constexpr int SK_U = 4;
-template <int NR>   // NR rows at once: their loads are in flight together
-__device__ __forceinline__ void slab_sum8(const Params& p, const int (&m)[NR], int n, float (&v)[NR][8]) {
-#pragma unroll
-  for (int q = 0; q < NR; ++q)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[q][j] = 0.f;
-  for (int s0 = 0; s0 < p.split; s0 += SK_U) {
-    f4 a[NR][SK_U], b[NR][SK_U];
-#pragma unroll
-    for (int u = 0; u < SK_U; ++u) {
-      const int su = min(s0 + u, p.split - 1);
-#pragma unroll
-      for (int q = 0; q < NR; ++q) {
-        const f4* src = reinterpret_cast<const f4*>(p.partial + ((size_t)su * p.M + m[q]) * p.Npad + n);
-        a[q][u] = src[0];
-        b[q][u] = src[1];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < SK_U; ++u) {
-      const bool in = s0 + u < p.split;
-#pragma unroll
-      for (int q = 0; q < NR; ++q)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          v[q][j] += in ? a[q][u][j] : 0.f;
-          v[q][4 + j] += in ? b[q][u][j] : 0.f;
-        }
-    }
-  }
-}
-
-// bias[n..n+7] + row_bias[b][n..n+7] as two vector loads each (scalar loads only for an unaligned
-// row_bias view), issued together instead of one dependent load per element
-__device__ __forceinline__ void epi_add8(const Params& p, int b, int n, float (&bi)[8], float (&rbv)[8]) {
-  f4 b0 = f4{}, b1 = f4{}, r0 = f4{}, r1 = f4{};
-  if (p.bias) {
-    const f4* q = reinterpret_cast<const f4*>(p.bias + n);
-    b0 = q[0];
-    b1 = q[1];
-  }
-  if (p.row_bias) {
-    const float* rb = p.row_bias + (size_t)b * p.rb_ld + n;
-    if (!((uintptr_t)rb & 15)) {
-      const f4* q = reinterpret_cast<const f4*>(rb);
-      r0 = q[0];
-      r1 = q[1];
-    } else {
-      r0 = f4{rb[0], rb[1], rb[2], rb[3]};
-      r1 = f4{rb[4], rb[5], rb[6], rb[7]};
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    bi[j] = b0[j];
-    bi[4 + j] = b1[j];
-    rbv[j] = r0[j];
-    rbv[4 + j] = r1[j];
-  }
-}
-
-__global__ void __launch_bounds__(256) splitk_reduce_kernel(Params p) {
-  const int groups = p.N / 8;
-  const size_t total = (size_t)p.M * groups;
-  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const int m = (int)(e / groups), n = (int)(e - (size_t)m * groups) * 8;
-    const int mo = out_row<true>(p, m);   // phase form (fp16 NHWC only): the slab row's output pixel; padding rows skipped
-    if (mo < 0) continue;
-    float vv[1][8];
-    slab_sum8<1>(p, {m}, n, vv);
-    float (&v)[8] = vv[0];
-    const int b = m / p.hw_out;
-    float bi[8], rbv[8];
-    epi_add8(p, b, n, bi, rbv);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = act_fn(p.act, (v[j] + bi[j]) + rbv[j]);
-    if (p.out_mode == SDK_OUT_NHWC_F16) {
-      h8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = (half_t)v[j];
-      if (p.res) {
-        h8 rr = ldg16(p.res + (size_t)m * p.res_ld + n);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (half_t)((float)o[j] + (float)rr[j]);
-      }
-      *reinterpret_cast<h8*>(reinterpret_cast<half_t*>(p.out) + (size_t)mo * p.out_ld + n) = o;
-    } else {
-      float* out = reinterpret_cast<float*>(p.out);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float x = v[j];
-        if (p.res) x += (float)p.res[(size_t)m * p.res_ld + n + j];
-        if (p.out_mode == SDK_OUT_NCHW_F32)
-          out[((size_t)b * p.N + n + j) * p.hw_out + (m - b * p.hw_out)] = x;
-        else
-          out[(size_t)m * p.out_ld + n + j] = x;
-      }
-    }
-  }
-}
-
-// Split-K reduction + epilogue that also emits the GroupNorm statistics of its rows (p.gnp):
-// grid (batch * gn_nch, ceil(N / 64)); 256 threads = 32 row lanes x 8 column octets over one chunk
-// (hw_out / gn_nch rows of one image); per-lane pivot-shifted sums, Chan merge of the 32 row lanes
-// through LDS, one (mean, M2) per chunk and channel.
-__global__ void __launch_bounds__(256) splitk_reduce_gn_kernel(Params p) {
-  __shared__ float2 red[32][64];
-  const int tc = threadIdx.x & 7, tr = threadIdx.x >> 3;
-  const int b = blockIdx.x / p.gn_nch, chunk = blockIdx.x - b * p.gn_nch;
-  // phase form: an image's rows in chunk order are phase major (4 * hw_out of them); row ri of the image is
-  // slab row ph * ph_rows_pad + b * hw_out + rem and output pixel (b, 2i + a, 2j + b)
-  const int R = (p.phase ? 4 : 1) * p.hw_out / p.gn_nch;
-  auto row_of = [&](int ri, int& mv, int& mo) __attribute__((always_inline)) {
-    if (!p.phase) {
-      mv = mo = b * p.hw_out + ri;
-      return;
-    }
-    const int ph = ri / p.hw_out, rem = ri - ph * p.hw_out;
-    const int i = rem / p.wo, j = rem - i * p.wo;
-    mv = ph * p.ph_rows_pad + b * p.hw_out + rem;
-    mo = (b * 2 * p.ho + 2 * i + (ph >> 1)) * (2 * p.wo) + 2 * j + (ph & 1);
-  };
-  const int n = blockIdx.y * 64 + tc * 8;
-  const bool colok = n < p.N;
-  GnAcc ga;
-  float bi[8], rbv[8];
-  if (colok) epi_add8(p, b, n, bi, rbv);   // the thread's columns and image are fixed
-  for (int r = tr; r < R && colok; r += 64) {   // rows r and r + 32 together
-    const bool two = r + 32 < R;
-    int mm[2], mo[2];
-    row_of(chunk * R + r, mm[0], mo[0]);
-    row_of(chunk * R + (two ? r + 32 : r), mm[1], mo[1]);
-    h8 rr[2] = {h8{}, h8{}};
-    if (p.res) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q) rr[q] = ldg16(p.res + (size_t)mm[q] * p.res_ld + n);
-    }
-    float v[2][8];
-    slab_sum8<2>(p, mm, n, v);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      if (q == 1 && !two) break;
-      h8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = (half_t)act_fn(p.act, (v[q][j] + bi[j]) + rbv[j]);
-      if (p.res) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (half_t)((float)o[j] + (float)rr[q][j]);
-      }
-      *reinterpret_cast<h8*>(reinterpret_cast<half_t*>(p.out) + (size_t)mo[q] * p.out_ld + n) = o;
-      gn_acc_add(ga, o, r == tr && q == 0);
-    }
-  }
-  const int cnt = R > tr ? (R - tr + 31) / 32 : 0;
-  if (cnt > 0 && colok) {
-    const float inv = 1.f / (float)cnt;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      red[tr][tc * 8 + j] = make_float2(ga.piv[j] + ga.s1[j] * inv, fmaxf(ga.s2[j] - ga.s1[j] * ga.s1[j] * inv, 0.f));
-  }
-  __syncthreads();
-  const int c = threadIdx.x, nn = blockIdx.y * 64 + c;
-  if (c >= 64 || nn >= p.N) return;
-  float2 acc = red[0][c];
-  float na = (float)((R + 31) / 32);
-  for (int t = 1; t < 32 && t < R; ++t) {
-    const float nb = (float)((R - t + 31) / 32);
-    const float2 q = red[t][c];
-    const float dl = q.x - acc.x, f = nb / (na + nb);
-    acc.x += dl * f;
-    acc.y += q.y + dl * dl * na * f;
-    na += nb;
-  }
-  p.gnp[((size_t)b * p.gn_nch + chunk) * p.N + nn] = acc;
-}
-
-// Direct convolution for a handful of output channels (variant 34): the UNet's conv_out (320 -> 4)
-// and the VAE decoder's conv_out (128 -> 3).  The implicit GEMM pads N to a 128-wide tile (32-43x
-// wasted MFMA work) and re-reads every input pixel per tap through LDS-DMA; here a workgroup owns an
-// 8 x 32 output patch, stages its (8+2) x (32+2) input halo of one 64-channel block in LDS once, and
-// each thread accumulates its pixel's <= 8 outputs with v_dot2_f32_f16 from the halo and the
-// block's weights (LDS broadcast reads).  Input read ~1.3x once; the FMAs run on the vector ALUs.
-constexpr int DC_TX = 32, DC_LD = BK + 8;
-constexpr int DC_MAXN = 8;
-
-// TY output rows x 32 columns per workgroup; QS threads per pixel split the 64-channel block
-// (QS = 4: 2 x 32 pixels, each thread 16 channels — 4x the threads for the small UNet maps, partial
-// sums reduced through LDS; QS = 1: 8 x 32 pixels, one thread per pixel — the 512x512 VAE map)
-template <int NO, int TY, int QS>
-__global__ void __launch_bounds__(256) conv_direct_kernel(Params p) {
-  constexpr int HY = TY + 2, HX = DC_TX + 2, CPQ = BK / QS;   // halo rows / cols, channels per thread
-  static_assert(TY * DC_TX * QS == 256, "one thread per (pixel, channel split)");
-  __shared__ __attribute__((aligned(16))) half_t xs[HY * HX * DC_LD];
-  __shared__ __attribute__((aligned(16))) half_t ws[NO * 9 * BK];
-  __shared__ float red[QS > 1 ? QS * TY * DC_TX * NO : 1];
-  const Seg& g = p.seg[0];
-  const int tid = threadIdx.x;
-  const int tiles_x = (p.wo + DC_TX - 1) / DC_TX, tiles_y = (p.ho + TY - 1) / TY;
-  const int b = blockIdx.x / (tiles_x * tiles_y), t = blockIdx.x - b * tiles_x * tiles_y;
-  const int oy0 = (t / tiles_x) * TY, ox0 = (t % tiles_x) * DC_TX;
-  const int pix = tid % (TY * DC_TX), q = tid / (TY * DC_TX);
-  const int ty = pix / DC_TX, tx = pix % DC_TX;
-  // halo origin: input (oy0 - org, ox0 - org); 3x3 taps read halo (ty + ky, tx + kx), a 1x1 reads its centre
-  const int ks = g.ksize, org = ks == 3 ? g.pad : 1, off = ks == 3 ? 0 : 1;
-  float acc[NO];
-#pragma unroll
-  for (int o = 0; o < NO; ++o) acc[o] = 0.f;
-  const int nblk = g.cin_pad / BK;
-  for (int cb = 0; cb < nblk; ++cb) {
-    // halo: HY x HX pixels x 64 channels, 16-B vectors; zeros outside the image (pad) and past cin
-    for (int e = tid; e < HY * HX * (BK / 8); e += 256) {
-      const int px = e / (BK / 8), v = e - px * (BK / 8);
-      const int hy = px / HX, hx = px - hy * HX;
-      const int iy = oy0 - org + hy, ix = ox0 - org + hx;
-      const int c = cb * BK + v * 8;
-      h8 val = {};
-      if ((unsigned)iy < (unsigned)g.h && (unsigned)ix < (unsigned)g.w && c < g.cin)
-        val = *reinterpret_cast<const h8*>(g.src0 + ((size_t)(b * g.h + iy) * g.w + ix) * g.ld0 + c);
-      *reinterpret_cast<h8*>(xs + px * DC_LD + v * 8) = val;
-    }
-    // weights of the block: packed row n, columns (cb * taps + tap) * 64 + j
-    for (int e = tid; e < NO * ks * ks * (BK / 8); e += 256) {
-      const int n = e / (ks * ks * (BK / 8)), r = e - n * (ks * ks * (BK / 8));
-      const int tap = r / (BK / 8), v = r - tap * (BK / 8);
-      h8 wv = {};
-      if (n < p.N) wv = *reinterpret_cast<const h8*>(p.W + (size_t)n * p.ldw + (size_t)(cb * ks * ks + tap) * BK + v * 8);
-      *reinterpret_cast<h8*>(ws + (n * 9 + tap) * BK + v * 8) = wv;
-    }
-    __syncthreads();
-    for (int tap = 0; tap < ks * ks; ++tap) {
-      const int dy = tap / ks + off, dx = tap % ks + off;
-      const half_t* xr = xs + ((ty + dy) * HX + tx + dx) * DC_LD + q * CPQ;
-#pragma unroll
-      for (int v = 0; v < CPQ / 8; ++v) {
-        const h8 xv = *reinterpret_cast<const h8*>(xr + v * 8);
-#pragma unroll
-        for (int o = 0; o < NO; ++o) {
-          const h8 wv = *reinterpret_cast<const h8*>(ws + (o * 9 + tap) * BK + q * CPQ + v * 8);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const h2 xa = {xv[2 * j], xv[2 * j + 1]}, wa = {wv[2 * j], wv[2 * j + 1]};
-            acc[o] = __builtin_amdgcn_fdot2(xa, wa, acc[o], false);
-          }
-        }
-      }
-    }
-    __syncthreads();
-  }
-  if constexpr (QS > 1) {
-#pragma unroll
-    for (int o = 0; o < NO; ++o) red[(q * TY * DC_TX + pix) * NO + o] = acc[o];
-    __syncthreads();
-    if (q != 0) return;
-#pragma unroll
-    for (int o = 0; o < NO; ++o) {
-      float a = acc[o];
-#pragma unroll
-      for (int k = 1; k < QS; ++k) a += red[(k * TY * DC_TX + pix) * NO + o];
-      acc[o] = a;
-    }
-  }
-  const int oy = oy0 + ty, ox = ox0 + tx;
-  if (oy >= p.ho || ox >= p.wo) return;
-  const int m = (b * p.ho + oy) * p.wo + ox;
-#pragma unroll
-  for (int o = 0; o < NO; ++o) {
-    if (o >= p.N) break;
-    const float val = acc[o] + (p.bias ? p.bias[o] : 0.f);
-    if (p.out_mode == SDK_OUT_NCHW_F32)
-      reinterpret_cast<float*>(p.out)[((size_t)b * p.N + o) * p.hw_out + oy * p.wo + ox] = val;
-    else if (p.out_mode == SDK_OUT_ROWS_F32)
-      reinterpret_cast<float*>(p.out)[(size_t)m * p.out_ld + o] = val;
-    else
-      reinterpret_cast<half_t*>(p.out)[(size_t)m * p.out_ld + o] = (half_t)val;
-  }
-}
-
-// pixel tiles: 8 x 32 with one thread per pixel when that already fills the chip (>= 4 workgroups
-// per CU), else 2 x 32 with four channel splits per pixel
-template <int NO>
-int launch_direct_n(const Params& p, hipStream_t s) {
-  const int big = ((p.wo + DC_TX - 1) / DC_TX) * ((p.ho + 7) / 8) * p.batch;
-  if (big >= 1024) {
-    hipLaunchKernelGGL((conv_direct_kernel<NO, 8, 1>), dim3(big), dim3(256), 0, s, p);
-  } else {
-    const int small = ((p.wo + DC_TX - 1) / DC_TX) * ((p.ho + 1) / 2) * p.batch;
-    hipLaunchKernelGGL((conv_direct_kernel<NO, 2, 4>), dim3(small), dim3(256), 0, s, p);
-  }
-  return check_launch("conv_direct");
-}
-
-int launch_direct(const Params& p, hipStream_t s) {
-  return p.N <= 4 ? launch_direct_n<4>(p, s) : launch_direct_n<8>(p, s);
-}
-
-// Skinny GEMM for M <= 64 rows (variant 35): the time-embedding MLP and the ResBlock embedding
-// projections run at M = batch (16 at the bench), where a 128-row tile wastes 7/8 of its MFMA work
-// and the 1280 x 20160 weight is streamed by a few dozen workgroups (~30 us per launch).  Here a
-// workgroup owns 16 output columns and its 4 waves split K; each lane streams 16-B pieces of its
-// column's packed weight row straight from HBM (every weight byte is read once, SK_PF K-steps in
-// flight), the A fragments (x rows, SiLU applied on load) come from L2, v_mfma_f32_16x16x32_f16
-// accumulates M/16 row blocks per weight fragment, and the 4 wave partials are summed through LDS.
-// 16x16x32 operand layout: lane l supplies A[row l%16][k 8(l/16)..+8] and B[k 8(l/16)..+8][col l%16];
-// D element i of lane l is D[4(l/16) + i][l%16].
-constexpr int SK_MAXM = 64, SK_PF = 8;
-
-template <int MB>   // 16-row blocks
-__global__ void __launch_bounds__(256) conv_skinny_kernel(Params p) {
-  __shared__ float red[4][MB][4][64];
-  const Seg& g = p.seg[0];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n0 = blockIdx.x * 16, K = g.cin;
-  const int ksteps = (K + 31) / 32, per = (ksteps + 3) / 4;
-  const int kb = min(ksteps, wave * per), ke = min(ksteps, kb + per);
-  const int kl = (lane >> 4) * 8;
-  const half_t* wrow = p.W + (size_t)(n0 + (lane & 15)) * p.ldw;   // rows < wrows (N padded to 128)
-  f4 acc[MB];
-#pragma unroll
-  for (int mb = 0; mb < MB; ++mb) acc[mb] = f4{};
-  for (int k0 = kb; k0 < ke; k0 += SK_PF) {
-    h8 w[SK_PF];
-#pragma unroll
-    for (int u = 0; u < SK_PF; ++u) {
-      const int k = (k0 + u) * 32 + kl;
-      w[u] = (k0 + u < ke && k < K) ? ldg16(wrow + k) : h8{};
-    }
-#pragma unroll
-    for (int u = 0; u < SK_PF; ++u) {
-      if (k0 + u >= ke) break;
-      const int k = (k0 + u) * 32 + kl;
-#pragma unroll
-      for (int mb = 0; mb < MB; ++mb) {
-        const int row = mb * 16 + (lane & 15);
-        h8 a = {};
-        if (row < p.M && k < K) {
-          a = ldg16(g.src0 + (size_t)row * g.ld0 + k);
-          if (g.silu) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              const float x = (float)a[j];
-              a[j] = (half_t)(x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)));
-            }
-          }
-        }
-        acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, w[u], acc[mb], 0, 0, 0);
-      }
-    }
-  }
-#pragma unroll
-  for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) red[wave][mb][i][lane] = acc[mb][i];
-  __syncthreads();
-  for (int e = tid; e < MB * 4 * 64; e += 256) {
-    const int mb = e / 256, i = (e >> 6) & 3, l = e & 63;
-    const int row = mb * 16 + 4 * (l >> 4) + i, n = n0 + (l & 15);
-    if (row >= p.M || n >= p.N) continue;
-    float v = red[0][mb][i][l] + red[1][mb][i][l] + red[2][mb][i][l] + red[3][mb][i][l];
-    if (p.bias) v += p.bias[n];
-    if (p.row_bias) v += p.row_bias[(size_t)(row / p.hw_out) * p.rb_ld + n];
-    v = act_fn(p.act, v);
-    if (p.res) v += (float)p.res[(size_t)row * p.res_ld + n];
-    if (p.out_mode == SDK_OUT_ROWS_F32)
-      reinterpret_cast<float*>(p.out)[(size_t)row * p.out_ld + n] = v;
-    else
-      reinterpret_cast<half_t*>(p.out)[(size_t)row * p.out_ld + n] = (half_t)v;
-  }
-}
-
-int launch_skinny(const Params& p, hipStream_t s) {
-  const dim3 grid((p.N + 15) / 16);
-  if (p.M <= 16) hipLaunchKernelGGL(conv_skinny_kernel<1>, grid, dim3(256), 0, s, p);
-  else if (p.M <= 32) hipLaunchKernelGGL(conv_skinny_kernel<2>, grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(conv_skinny_kernel<4>, grid, dim3(256), 0, s, p);
-  return check_launch("conv_skinny");
-}
-
-#endif  // SDK_PART(0)
 
 template <class CF, int SIMPLE>
 int launch_glds_as(const Params& p, hipStream_t s) {
@@ -2704,84 +1781,6 @@ int launch_glds(const Params& p, hipStream_t s) {
   }
 }
 
-// ---------------------------------------------------------------------- the variant table
-// One row per variant id; the planner, the part launchers, the dispatch of sdk_conv2d and sdk_kernel_name
-// all read it, and nothing else says what an id means.  A row's columns:
-//   id | kernel family | config type (its TBM x TBN is the tile) | DBG mask (DIAG only) |
-//   workgroups per CU for the planner's fill estimate (not Cfg::OCC: 4 shares a CU at OCC 1) |
-//   whether the epilogue pairs the (x, gate) halves of a GEGLU projection | sdk_kernel_name
-// The sublist a row sits in is the compile part that instantiates its kernel (below).  Families: NONE no such id;
-// IGEMM register-staged conv_igemm_kernel; GLDS the LDS-DMA tile conv_glds_kernel; PH32 / PH16 the phased 256x256
-// conv_ph_kernel on 32x32x16 / 16x16x32; DIRECT (<= 8 output channels); SKINNY (<= 64 rows); DIAG a phased
-// ablation (wrong outputs by design, launched by the diagnostics build only); RETIRED named, never planned.
-enum class Fam { NONE, IGEMM, GLDS, PH32, PH16, DIRECT, SKINNY, DIAG, RETIRED };
-struct CfgIgemm { static constexpr int TBM = BM, TBN = BN; };
-struct CfgUntiled { static constexpr int TBM = 0, TBN = 0; };   // direct / skinny: no BM x BN tiling
-template <class CF> struct TileOf { static constexpr int TBM = CF::TBM, TBN = CF::TBN; };
-template <int S, int D> struct TileOf<PhCfg<S, D>> { static constexpr int TBM = 256, TBN = 256; };
-
-// variant 5 (256x320 on 32x32x16, 16 waves) spilled at the 128-VGPR cap of 4 waves per SIMD; its row keeps the
-// name and carries the config of 22, the same tile on 16x16x32, which a forced 5 runs as.  36 / 37 (halo tiles)
-// and 39 (the 8-wave 256x320 on 32x32x16, spilled, never built) have no row: unknown.
-#define SDK_CONV_VARIANTS_P0(X, P)                                                                      \
-  X(P, 0, IGEMM, CfgIgemm, 0, 2, true, "conv_igemm_kernel")                                             \
-  X(P, 5, RETIRED, Cfg256x320m, 0, 1, false, "conv_glds_kernel<Cfg<256,320,8,2>>")                      \
-  X(P, 34, DIRECT, CfgUntiled, 0, 1, false, "conv_direct_kernel")                                       \
-  X(P, 35, SKINNY, CfgUntiled, 0, 1, false, "conv_skinny_kernel")
-#define SDK_CONV_VARIANTS_P1(X, P)                                                                      \
-  X(P, 2, GLDS, Cfg256x256, 0, 1, true, "conv_glds_kernel<Cfg<256,256,2,4>>")                           \
-  X(P, 3, GLDS, Cfg256x128, 0, 1, true, "conv_glds_kernel<Cfg<256,128,4,2>>")                           \
-  X(P, 4, GLDS, Cfg128x128, 0, 2, true, "conv_glds_kernel<Cfg<128,128,2,2>>")                           \
-  X(P, 6, GLDS, Cfg256x160, 0, 1, false, "conv_glds_kernel<Cfg<256,160,8,1>>")                          \
-  X(P, 7, GLDS, Cfg128x320, 0, 1, false, "conv_glds_kernel<Cfg<128,320,4,2>>")
-#define SDK_CONV_VARIANTS_P2(X, P)                                                                      \
-  X(P, 16, GLDS, Cfg128x128r4, 0, 1, true, "conv_glds_kernel<Cfg<128,128,2,2,4>>")                      \
-  X(P, 17, GLDS, Cfg256x128r3, 0, 1, true, "conv_glds_kernel<Cfg<256,128,4,2,3>>")                      \
-  X(P, 18, GLDS, Cfg128x128r3, 0, 1, true, "conv_glds_kernel<Cfg<128,128,2,2,3>>")                      \
-  X(P, 19, GLDS, Cfg128x256r3, 0, 1, true, "conv_glds_kernel<Cfg<128,256,2,4,3>>")                      \
-  X(P, 22, GLDS, Cfg256x320m, 0, 1, false, "conv_glds_kernel<Cfg<256,320,8,2,2,m16>>")                  \
-  X(P, 23, GLDS, Cfg128x320m, 0, 1, false, "conv_glds_kernel<Cfg<128,320,4,2,2,m16>>")
-#define SDK_CONV_VARIANTS_P3(X, P)                                                                      \
-  X(P, 24, GLDS, Cfg256x160m, 0, 1, false, "conv_glds_kernel<Cfg<256,160,8,1,2,m16>>")                  \
-  X(P, 25, GLDS, Cfg128x256r3m, 0, 1, true, "conv_glds_kernel<Cfg<128,256,2,4,3,m16>>")                 \
-  X(P, 26, GLDS, Cfg128x128r3m, 0, 1, true, "conv_glds_kernel<Cfg<128,128,2,2,3,m16>>")                 \
-  X(P, 31, GLDS, Cfg128x160o2m, 0, 2, false, "conv_glds_kernel<Cfg<128,160,4,1,2,m16,occ2>>")           \
-  X(P, 32, GLDS, Cfg128x128o2m, 0, 2, true, "conv_glds_kernel<Cfg<128,128,2,2,2,m16,occ2>>")            \
-  X(P, 33, GLDS, Cfg128x160r4m, 0, 1, false, "conv_glds_kernel<Cfg<128,160,4,1,4,m16>>")
-// the ablations are not named (sdk_kernel_name: "unknown"): no DMA, no MFMA, DMA from the zero page, no epilogue
-// stores, W / A from the zero page, no W / A DMA issued, A DMAs read W rows (cheap addressing, L2), A DMAs read
-// the centre tap (no masks / halo)
-#define SDK_CONV_VARIANTS_P4(X, P)                                                                      \
-  X(P, 8, PH32, PhCfg8, 0, 1, true, "conv_ph_kernel<256x256,ring8>")                                    \
-  X(P, 9, PH32, PhCfg10, 0, 1, true, "conv_ph_kernel<256x256,ring10>")                                  \
-  X(P, 20, PH16, PhCfg8, 0, 1, true, "conv_ph_kernel<256x256,ring8,m16>")                               \
-  X(P, 21, PH16, PhCfg10, 0, 1, true, "conv_ph_kernel<256x256,ring10,m16>")                             \
-  X(P, 10, DIAG, PhCfg8, 1, 1, true, "unknown")                                                         \
-  X(P, 11, DIAG, PhCfg8, 2, 1, true, "unknown")                                                         \
-  X(P, 12, DIAG, PhCfg8, 4, 1, true, "unknown")                                                         \
-  X(P, 13, DIAG, PhCfg8, 64, 1, true, "unknown")                                                        \
-  X(P, 14, DIAG, PhCfg8, 16, 1, true, "unknown")                                                        \
-  X(P, 15, DIAG, PhCfg8, 32, 1, true, "unknown")                                                        \
-  X(P, 27, DIAG, PhCfg8, 128, 1, true, "unknown")                                                       \
-  X(P, 28, DIAG, PhCfg8, 256, 1, true, "unknown")                                                       \
-  X(P, 29, DIAG, PhCfg8, 512, 1, true, "unknown")                                                       \
-  X(P, 30, DIAG, PhCfg8, 1024, 1, true, "unknown")
-// 8-wave 256-row tiles on 16x16x32 (64 / 128-row wave tiles)
-#define SDK_CONV_VARIANTS_P5(X, P)                                                                      \
-  X(P, 38, GLDS, Cfg256x320w8m, 0, 1, false, "conv_glds_kernel<Cfg<256,320,4,2,2,m16>>")                \
-  X(P, 40, GLDS, Cfg256x256w8m, 0, 1, true, "conv_glds_kernel<Cfg<256,256,2,4,2,m16>>")
-#define SDK_CONV_VARIANTS(X)                                                                            \
-  SDK_CONV_VARIANTS_P0(X, 0) SDK_CONV_VARIANTS_P1(X, 1) SDK_CONV_VARIANTS_P2(X, 2) SDK_CONV_VARIANTS_P3(X, 3) \
-  SDK_CONV_VARIANTS_P4(X, 4) SDK_CONV_VARIANTS_P5(X, 5)
-constexpr int kVariantIds = 41;      // ids are 0 .. 40 (a row past the end does not compile)
-constexpr int kRetiredRunsAs = 22;
-
-#ifdef SDK_CONV_DIAGNOSTICS
-constexpr bool kDiagnostics = true;
-#else
-constexpr bool kDiagnostics = false;
-#endif
-
 // A tile-kernel row's launch.  A template, so `if constexpr` keeps each row to its own family's kernel: a
 // kernel template is instantiated only in the part whose sublist names it.
 template <Fam F, class CF, int DBG>
@@ -2793,440 +1792,5 @@ int launch_variant(const Params& p, hipStream_t s) {
   else return fail(SDK_EINVAL, "conv2d: this build has no kernel for the planned variant");
 }
 
-// ---------------------------------------------------------------------- compile partition
-// build.py compiles this file once per part (-DSDK_CONV_PART=k, in parallel; one monolithic object took
-// ~10 minutes): part 0 holds the host planner, the ABI entry points and the small kernels, parts 1-5 the
-// tile-kernel instantiations, reached through these hidden C-linkage launchers (the kernel templates are
-// visible everywhere, each is instantiated only in the part whose launcher expands its row).  Without
-// SDK_CONV_PART every part is in one object.
-#define SDK_HIDDEN __attribute__((visibility("hidden")))
 }  // namespace
 }  // namespace sdk
-// Params lives in an anonymous namespace, so each part compiles its own copy of the type: the caller passes
-// its sizeof(Params) and a part whose layout differs (a part-only preprocessor state) refuses the launch
-#define SDK_PART_DECL(k) extern "C" SDK_HIDDEN int sdk_conv_launch_part##k(int v, const void* pp, int psize, void* st)
-#define SDK_LAUNCH_CASE(P, ID, FAM, CF, DBG, PER_CU, GEGLU, NAME) \
-    case ID: return launch_variant<Fam::FAM, CF, DBG>(p, s);
-#define SDK_PART_FN(k) SDK_PART_FN_(k)   /* k may itself be a macro (SDK_CONV_PART) */
-#define SDK_PART_FN_(k) SDK_PART_DECL(k) {                                                              \
-    using namespace sdk;                                                                               \
-    if (psize != (int)sizeof(Params))                                                                   \
-      return fail(SDK_EINVAL, "conv2d: Params layout differs between compile parts (" +                 \
-                                  std::to_string(psize) + " vs " + std::to_string(sizeof(Params)) + ")"); \
-    const Params& p = *static_cast<const Params*>(pp);                                                 \
-    const hipStream_t s = (hipStream_t)st;                                                              \
-    switch (v) { SDK_CONV_VARIANTS_P##k(SDK_LAUNCH_CASE, k) }                                           \
-    return fail(SDK_EINVAL, "conv2d: variant " + std::to_string(v) + " is not in this launcher part");  \
-  }
-SDK_PART_DECL(1); SDK_PART_DECL(2); SDK_PART_DECL(3); SDK_PART_DECL(4); SDK_PART_DECL(5);
-#if SDK_CONV_PART > 0   // this object's own part
-SDK_PART_FN(SDK_CONV_PART)
-#elif SDK_CONV_PART < 0
-SDK_PART_FN(1) SDK_PART_FN(2) SDK_PART_FN(3) SDK_PART_FN(4) SDK_PART_FN(5)
-#endif
-#if SDK_PART(0)
-namespace sdk {
-namespace {
-
-struct Variant { Fam fam; int part, bm, bn, per_cu; bool geglu; const char* name; };
-struct VariantTable { Variant row[kVariantIds]; };
-constexpr VariantTable make_variant_table() {
-  VariantTable t{};
-#define SDK_ROW(P, ID, FAM, CF, DBG, PER_CU, GEGLU, NAME) \
-  t.row[ID] = Variant{Fam::FAM, P, TileOf<CF>::TBM, TileOf<CF>::TBN, PER_CU, GEGLU, NAME};
-  SDK_CONV_VARIANTS(SDK_ROW)
-#undef SDK_ROW
-  return t;
-}
-constexpr VariantTable kVariants = make_variant_table();
-// the row of an id, nullptr when there is none
-inline const Variant* variant_row(int v) {
-  return v >= 0 && v < kVariantIds && kVariants.row[v].fam != Fam::NONE ? &kVariants.row[v] : nullptr;
-}
-constexpr int variant_of(Fam f) {   // the id of a one-kernel family
-  for (int v = 0; v < kVariantIds; ++v)
-    if (kVariants.row[v].fam == f) return v;
-  return -1;
-}
-constexpr int kIgemm = variant_of(Fam::IGEMM), kDirect = variant_of(Fam::DIRECT), kSkinny = variant_of(Fam::SKINNY);
-// the phase form's row map and the in-launch split live in conv_glds_kernel (and the split-K reduces)
-inline bool lds_dma_tile(const Variant& r) { return r.fam == Fam::GLDS; }
-// the fp16 epilogues that emit GroupNorm statistics without a split: conv_glds_kernel's and the phased 32x32x16 one
-inline bool emits_gn_stats(const Variant& r) { return r.fam == Fam::GLDS || r.fam == Fam::PH32; }
-using PartLaunch = int (*)(int, const void*, int, void*);
-constexpr PartLaunch kPartLaunch[] = {nullptr, sdk_conv_launch_part1, sdk_conv_launch_part2, sdk_conv_launch_part3,
-                                      sdk_conv_launch_part4, sdk_conv_launch_part5};
-
-#ifdef SDK_CONV_DIAGNOSTICS
-unsigned long long* g_conv_stamps = nullptr;   // 8 stamps x 65536 workgroups (SDK_CONV_STAMPS=1)
-constexpr int kStampWgs = 65536;
-#endif
-// benchmark override of the tile configuration, read once when the library loads
-const int g_env_variant = [] {
-  const char* fe = getenv("SDK_CONV_VARIANT");
-  return fe ? atoi(fe) : -1;
-}();
-
-// M-panels per tile group of an unsplit plan (item_coords): the caller's value, else M-panel major
-// (SDK_CONV_GM overrides the default, for measurements)
-int tile_group_m(const sdk_conv_args* a, const Params& p) {
-  static const int env_gm = getenv("SDK_CONV_GM") ? atoi(getenv("SDK_CONV_GM")) : 0;
-  const int g = a->tile_group_m > 0 ? a->tile_group_m : env_gm > 0 ? env_gm : 1;
-  return std::max(1, std::min(g, p.tiles_m));
-}
-
-// the plan of the direct and skinny kernels: one launch of `grid` workgroups, no split, no workspace, no
-// GroupNorm statistics
-void plan_untiled(Params& p, sdk_conv_plan_info* info, int variant, int tiles_n, int grid, int kt, double kreal) {
-  p.variant = variant; p.split = 1; p.tiles_m = 1; p.tiles_n = tiles_n; p.Npad = p.N; p.kt_per_split = kt;
-  if (info) {
-    info->split_k = 1; info->grid_tiles = grid; info->workspace_bytes = 0; info->variant = variant;
-    info->flops = 2.0 * p.M * (double)p.N * kreal; info->gn_chunks = 0;
-  }
-}
-
-int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
-  if (!a) return fail(SDK_EINVAL, "conv2d: null args");
-  if (a->nseg < 1 || a->nseg > 2) return fail(SDK_EINVAL, "conv2d: nseg must be 1 or 2");
-  if (a->batch <= 0 || a->ho <= 0 || a->wo <= 0 || a->cout <= 0)
-    return fail(SDK_EINVAL, "conv2d: empty output shape");
-  if (!a->weight || !a->out) return fail(SDK_EINVAL, "conv2d: null weight/out");
-  p = Params{};
-  if (a->act != SDK_ACT_NONE && a->act != SDK_ACT_QUICK_GELU) return fail(SDK_EINVAL, "conv2d: unknown act");
-  if (a->act != SDK_ACT_NONE && a->out_mode == SDK_OUT_GEGLU_F16)
-    return fail(SDK_EINVAL, "conv2d: act does not combine with the GEGLU epilogue");
-  p.act = a->act;
-  p.batch = a->batch; p.ho = a->ho; p.wo = a->wo; p.hw_out = a->ho * a->wo;
-  p.M = a->batch * p.hw_out;
-  p.N = a->cout;
-  p.nseg = a->nseg;
-  // phase form of nearest-x2 + 3x3 (Params::phase): the kernels see the low-res grid, four times
-  const bool phase = a->upsample_phase != 0;
-  if (phase) {
-    if (a->nseg != 1 || a->out_mode != SDK_OUT_NHWC_F16 || a->residual || a->row_bias || a->act != SDK_ACT_NONE ||
-        a->split_inlaunch || (a->ho & 1) || (a->wo & 1))
-      return fail(SDK_EINVAL, "conv2d: the phase form is one segment, fp16 NHWC, even output extents, no residual / "
-                              "row_bias / act / in-launch split");
-    if (a->weight_batch_stride <= 0)
-      return fail(SDK_EINVAL, "conv2d: the phase form needs the four phase matrices (weight_batch_stride)");
-    if ((double)a->batch * p.hw_out >= 2147483647.0 / 8) return fail(SDK_EINVAL, "conv2d: phase form: too many rows");
-    p.phase = 1;
-    p.ho = a->ho / 2; p.wo = a->wo / 2; p.hw_out = p.ho * p.wo;
-    p.ph_rows = p.ph_rows_pad = a->batch * p.hw_out;
-    p.M = 4 * p.ph_rows;   // the planner pads it per phase once the M-tile is known
-  }
-  double kreal = 0;
-  int kt = 0, koff = 0;
-  for (int s = 0; s < a->nseg; ++s) {
-    const sdk_conv_src& g = a->seg[s];
-    Seg& d = p.seg[s];
-    if (!g.src0) return fail(SDK_EINVAL, "conv2d: null src0");
-    if (g.cin <= 0 || g.cin % 8 || g.c_split % 8 || g.c_split <= 0 || g.c_split > g.cin)
-      return fail(SDK_EINVAL, "conv2d: cin/c_split must be positive multiples of 8 (c_split <= cin)");
-    if (g.c_split < g.cin && !g.src1) return fail(SDK_EINVAL, "conv2d: concat without src1");
-    if (g.ld0 % 8 || (g.c_split < g.cin && g.ld1 % 8)) return fail(SDK_EINVAL, "conv2d: ld must be a multiple of 8");
-    if (g.ksize != 1 && g.ksize != 3 && !(phase && g.ksize == 2))
-      return fail(SDK_EINVAL, "conv2d: ksize must be 1 or 3 (2: the phase form)");
-    if ((g.gn_scale == nullptr) != (g.gn_shift == nullptr)) return fail(SDK_EINVAL, "conv2d: gn scale/shift pair");
-    const int lh = g.upsample ? 2 * g.h : g.h, lw = g.upsample ? 2 * g.w : g.w;
-    if (g.pad_end < 0 || g.pad_end > 2 || (g.pad_end && g.upsample))
-      return fail(SDK_EINVAL, "conv2d: pad_end must be 0..2 (no upsample)");
-    // zero padding is implicit (taps outside the source read zeros), so pad_end only widens the grid
-    int eh = (lh + 2 * g.pad + g.pad_end - g.ksize) / g.stride + 1;
-    int ew = (lw + 2 * g.pad + g.pad_end - g.ksize) / g.stride + 1;
-    if (phase) {   // the source is the low-res image with its 1-pixel zero border; the output is the x2 image
-      if (g.ksize != 2 || g.stride != 1 || g.pad || g.pad_end || g.upsample || g.h < 3 || g.w < 3 || g.cin % BK ||
-          g.c_split != g.cin || g.gn_scale || g.silu)
-        return fail(SDK_EINVAL, "conv2d: the phase form reads one zero-bordered source with 2x2 taps, stride 1, "
-                                "pad 0, cin % 64 == 0, no transform");
-      eh = 2 * (g.h - 2);
-      ew = 2 * (g.w - 2);
-    }
-    if (eh != a->ho || ew != a->wo) return fail(SDK_EINVAL, "conv2d: output size does not match source geometry");
-    d.src0 = (const half_t*)g.src0; d.src1 = (const half_t*)g.src1;
-    d.gscale = g.gn_scale; d.gshift = g.gn_shift;
-    d.c_split = g.c_split; d.cin = g.cin; d.cin_pad = (g.cin + BK - 1) / BK * BK;
-    d.ld0 = g.ld0; d.ld1 = g.ld1; d.h = g.h; d.w = g.w; d.ksize = g.ksize; d.stride = g.stride; d.pad = g.pad;
-    d.upsample = g.upsample; d.silu = g.silu;
-    d.k_off = koff; d.tiles_per_tap = d.cin_pad / BK; d.kt_begin = kt;
-    const int taps = g.ksize * g.ksize;
-    kt += taps * d.tiles_per_tap;
-    koff += taps * d.cin_pad;
-    kreal += (double)taps * g.cin;
-  }
-  if (koff != a->k_total) return fail(SDK_EINVAL, "conv2d: k_total does not match the packed segment layout");
-  {
-    const sdk_conv_src& g = a->seg[0];
-    p.nomask = g.pad == 0 && g.pad_end == 0 && !g.upsample && g.cin % BK == 0 &&
-               (g.c_split == g.cin || g.c_split % BK == 0) && g.gn_scale == nullptr && !g.silu;
-    // the linear K loop of the LDS-DMA kernels (conv_glds_kernel SIMPLE): one segment, one source, no masks
-    const sdk_conv_src& g1 = a->seg[1];
-    const bool one_src = !g.src1 || g.c_split >= g.cin;
-    // a second segment qualifies when it is a plain 1x1 over the output grid (the fused ResBlock shortcut)
-    const bool lin1 = a->nseg == 2 && g1.ksize == 1 && g1.stride == 1 && g1.pad == 0 && g1.pad_end == 0 &&
-                      !g1.upsample && g1.cin % BK == 0 && (!g1.src1 || g1.c_split >= g1.cin || g1.c_split % BK == 0) &&
-                      g1.gn_scale == nullptr && !g1.silu && g1.h == a->ho && g1.w == a->wo;
-    p.simple = !(p.nomask && one_src) ? 0 : a->nseg == 1 ? 1 : lin1 ? 2 : 0;
-  }
-  if (a->out_mode == SDK_OUT_NHWC_F16 || a->out_mode == SDK_OUT_GEGLU_F16) {
-    if (a->cout % 8 || a->out_ld % 8 || (a->residual && a->res_ld % 8))
-      return fail(SDK_EINVAL, "conv2d: fp16 NHWC output needs cout/out_ld/res_ld multiples of 8");
-  }
-  if (a->out_mode == SDK_OUT_GEGLU_F16 && (a->cout % 64)) return fail(SDK_EINVAL, "conv2d: GEGLU cout % 64");
-  p.kt_total = kt;
-  p.W = (const half_t*)a->weight; p.ldw = a->k_total; p.wrows = (a->cout + 127) / 128 * 128;
-  p.wbs = a->weight_batch_stride;
-  if (p.wbs < 0 || (p.wbs && p.wbs < (long long)p.wrows * p.ldw))
-    return fail(SDK_EINVAL, "conv2d: weight_batch_stride smaller than one packed weight matrix");
-  p.bias = a->bias; p.row_bias = a->row_bias; p.rb_ld = a->row_bias_ld;
-  p.res = (const half_t*)a->residual; p.res_ld = a->res_ld;
-  p.out = a->out; p.out_ld = a->out_ld; p.out_mode = a->out_mode;
-  bool transform = false;
-  for (int s = 0; s < a->nseg; ++s) {
-    const sdk_conv_src& g = a->seg[s];
-    transform |= (g.gn_scale != nullptr) || g.silu;
-    // the LDS-DMA kernels: buffer resources (31-bit byte offsets), a K-step's 64 channels
-    // from one concat source, and a second segment that is a plain 1x1 over the output grid
-    if ((double)a->batch * g.h * g.w * std::max(g.ld0, g.ld1) * 2 >= 2147483647.0) transform = true;
-    if (g.c_split < g.cin && g.c_split % BK) transform = true;
-    if (s == 1 && (g.ksize != 1 || g.stride != 1 || g.pad != 0 || g.pad_end || g.upsample || g.h != a->ho || g.w != a->wo))
-      transform = true;
-  }
-  if ((double)((a->cout + 127) / 128 * 128) * a->k_total * 2 >= 2147483647.0) transform = true;
-  if (a->act != SDK_ACT_NONE) transform = true;   // the CLIP fc1 (once per prompt, not per step)
-  // tile configuration: LDS-DMA kernels for transform-free operands, scored by
-  // padded-work efficiency x whole-chip wave quantisation x measured per-config
-  // throughput
-  struct Opt { int variant; double pref; };
-  // relative throughput of each config on shapes it tiles exactly (tools/bench_conv.py, MI355X)
-  const Opt opts[] = {{8, 1.05}, {2, 1.00}, {22, 0.92}, {7, 0.88}, {6, 0.72}, {4, 0.72}, {3, 0.65}};
-  int var = kIgemm, best_split = 0;
-  auto pick_split = [&](int tiles, int slots, double& fill) {
-    int best = 1;
-    double bf = -1;
-    for (int sp = 1; sp <= 16; sp *= 2) {
-      if (sp > 1 && kt / sp < 8) break;
-      const int blocks = tiles * sp;
-      const double waves = (double)((blocks + slots - 1) / slots);
-      double f = (double)blocks / (waves * slots);
-      for (int q = 1; q < sp; q *= 2) f *= 0.95;      // slab write + reduce traffic
-      if (f > bf + 1e-9) { bf = f; best = sp; }
-    }
-    fill = bf;
-    return best;
-  };
-  if (p.wbs && transform) return fail(SDK_EINVAL, "conv2d: per-image weights need a transform-free operand");
-  if (phase && p.simple != 1) return fail(SDK_EINVAL, "conv2d: the phase form runs on the linear A issue only");
-  if (!transform) {
-    double best = -1;
-    for (const Opt& o : opts) {
-      const Variant& r = kVariants.row[o.variant];
-      if (a->out_mode == SDK_OUT_GEGLU_F16 && !r.geglu) continue;
-      if (phase ? !lds_dma_tile(r) : (p.wbs && p.hw_out % r.bm)) continue;   // per-image weights: M-tiles inside one image
-      const int tmm = phase ? 4 * ((p.ph_rows + r.bm - 1) / r.bm) : (p.M + r.bm - 1) / r.bm;
-      const int tnn = (p.N + r.bn - 1) / r.bn;
-      const double eff = (double)p.M * p.N / ((double)tmm * r.bm * tnn * r.bn);
-      double fill;
-      const bool can_split = a->out_mode != SDK_OUT_GEGLU_F16 && a->cout % 8 == 0;
-      const int slots = 256 * r.per_cu;
-      const int sp = can_split ? pick_split(tmm * tnn, slots, fill) : 1;
-      if (!can_split) {
-        const int blocks = tmm * tnn;
-        fill = (double)blocks / ((double)((blocks + slots - 1) / slots) * slots);
-      }
-      const double score = eff * fill * o.pref;
-      if (score > best) { best = score; var = o.variant; best_split = sp; }
-    }
-  }
-  // forced configuration: the caller's autotuner (variant_hint = 1 + id) or, for
-  // benchmarks, SDK_CONV_VARIANT=id (read once, at library load)
-  int forced = a->variant_hint > 0 ? a->variant_hint - 1 : g_env_variant;
-  // variant 34: direct convolution for <= 8 output channels (conv_out of the UNet / VAE decoder)
-  {
-    const sdk_conv_src& g = a->seg[0];
-    const bool direct_ok = a->nseg == 1 && a->cout <= DC_MAXN && (g.ksize == 3 || (g.ksize == 1 && g.pad == 0)) &&
-                           g.stride == 1 && !g.upsample && g.pad_end == 0 && g.pad <= 1 && g.c_split == g.cin &&
-                           g.gn_scale == nullptr && !g.silu && !a->residual && !a->row_bias &&
-                           a->act == SDK_ACT_NONE && a->out_mode != SDK_OUT_GEGLU_F16 && !p.wbs;
-    if (forced == kDirect && !direct_ok) return fail(SDK_EINVAL, "conv2d: variant 34 (direct) does not fit this conv");
-    if (direct_ok && (forced < 0 || forced == kDirect)) {
-      plan_untiled(p, info, kDirect, 1, ((a->wo + DC_TX - 1) / DC_TX) * ((a->ho + 7) / 8) * a->batch, kt, kreal);
-      if (a->gn_partial) return fail(SDK_EINVAL, "conv2d: the direct variant emits no GroupNorm statistics");
-      return SDK_OK;
-    }
-  }
-  // variant 35: skinny GEMM for <= 64 rows (token GEMMs at M = batch: the time-embedding MLP)
-  {
-    const sdk_conv_src& g = a->seg[0];
-    const bool skinny_ok = a->nseg == 1 && p.M <= SK_MAXM && g.ksize == 1 && g.stride == 1 && g.pad == 0 &&
-                           g.pad_end == 0 && !g.upsample && g.c_split == g.cin && g.gn_scale == nullptr &&
-                           (a->out_mode == SDK_OUT_NHWC_F16 || a->out_mode == SDK_OUT_ROWS_F32) && !a->gn_partial &&
-                           !p.wbs;
-    if (forced == kSkinny && !skinny_ok) return fail(SDK_EINVAL, "conv2d: variant 35 (skinny) does not fit this GEMM");
-    if (skinny_ok && (forced < 0 || forced == kSkinny)) {
-      plan_untiled(p, info, kSkinny, (p.N + 15) / 16, (p.N + 15) / 16, kt, kreal);
-      return SDK_OK;
-    }
-  }
-  // What a forced id means is its row of the variant table.  The diagnostic ablations compute wrong outputs by
-  // design: the product library rejects them, only the separate diagnostics build (-DSDK_CONV_DIAGNOSTICS,
-  // libsdk_amd_diag.so) runs them.
-  const Variant* fr = variant_row(forced);
-  if (fr && fr->fam == Fam::DIAG && !kDiagnostics)
-    return fail(SDK_EINVAL, "conv2d: variant " + std::to_string(forced) +
-                                " is a diagnostic ablation (only in libsdk_amd_diag.so)");
-  if (forced >= 0 && !fr) return fail(SDK_EINVAL, "conv2d: unknown variant " + std::to_string(forced));
-  // a forced 5 (a leftover SDK_CONV_VARIANT=5 or an old tuning entry) runs as 22, the same 256x320 tile on 16x16x32
-  // (which is not spill-free either: 8 to 16 B/lane of scratch in build*/resource_usage.txt), with a one-time warning
-  if (fr && fr->fam == Fam::RETIRED) {
-    static std::atomic<bool> warned{false};
-    if (!warned.exchange(true))
-      fprintf(stderr, "sd_amd conv2d: variant 5 is retired; running the same 256x320 tile as variant 22\n");
-    forced = kRetiredRunsAs;
-    fr = &kVariants.row[forced];
-  }
-  // honoured when the kernel can run this conv: the register-staged kernel takes every operand but per-image
-  // weights, the others need a transform-free one, a GEGLU-pairing epilogue for the GEGLU output, the LDS-DMA
-  // tile family for the phase form, and per-image weights need M-tiles inside one image
-  if (fr && (fr->fam == Fam::IGEMM || !transform) && (fr->geglu || a->out_mode != SDK_OUT_GEGLU_F16) &&
-      (phase ? lds_dma_tile(*fr) : (!p.wbs || (fr->fam != Fam::IGEMM && p.hw_out % fr->bm == 0)))) {
-    var = forced;
-    best_split = 0;
-  }
-  const Variant& row = kVariants.row[var];
-  const int tbm = row.bm, tbn = row.bn;
-  if (phase) {
-    if (!lds_dma_tile(row)) return fail(SDK_EINVAL, "conv2d: the phase form found no LDS-DMA tile plan");
-    p.ph_rows_pad = (p.ph_rows + tbm - 1) / tbm * tbm;   // no M-tile straddles two phases
-    p.M = 4 * p.ph_rows_pad;
-  } else if (p.wbs && (row.fam == Fam::IGEMM || p.hw_out % tbm)) {
-    return fail(SDK_EINVAL, "conv2d: per-image weights: no LDS-DMA tile fits inside one image");
-  }
-  p.variant = var;
-  p.tiles_m = (p.M + tbm - 1) / tbm;
-  p.tiles_n = (p.N + tbn - 1) / tbn;
-  p.Npad = p.tiles_n * tbn;                       // split-K slab row stride
-  const int tiles = p.tiles_m * p.tiles_n;
-  int split = a->split_k;
-  if (split <= 0) {
-    if (best_split > 0) {
-      split = best_split;
-    } else {
-      split = 1;
-      while (tiles * split < 256 * row.per_cu && kt / (split * 2) >= 8 && split < 16) split *= 2;
-    }
-  }
-  if (a->out_mode == SDK_OUT_GEGLU_F16 || a->cout % 8) split = 1;
-  if (split > kt) split = kt;
-  p.kt_per_split = (kt + split - 1) / split;
-  split = (kt + p.kt_per_split - 1) / p.kt_per_split;
-  p.split = split;
-  p.gm = split == 1 ? tile_group_m(a, p) : 1;
-#ifdef SDK_CONV_DIAGNOSTICS
-  if (getenv("SDK_CONV_STAMPS")) {
-    if (!g_conv_stamps && (hipMalloc((void**)&g_conv_stamps, (size_t)kStampWgs * 8 * 8) != hipSuccess ||
-                           hipMemset(g_conv_stamps, 0, (size_t)kStampWgs * 8 * 8) != hipSuccess)) g_conv_stamps = nullptr;
-    if ((long long)p.tiles_m * p.tiles_n * p.split <= kStampWgs) p.stamps = g_conv_stamps;
-    p.stamps_rt = atoi(getenv("SDK_CONV_STAMPS")) == 2;
-  }
-#endif
-  int64_t ws = split > 1 ? (int64_t)split * p.M * p.Npad * 4 : 0;
-  if (a->split_inlaunch) {
-    if (!lds_dma_tile(row))
-      return fail(SDK_EINVAL, "conv2d: in-launch split-K needs an LDS-DMA tile plan (a conv_glds_kernel variant)");
-    if (split != 2) return fail(SDK_EINVAL, "conv2d: in-launch split-K combines exactly two K halves (split_k = 2)");
-    if (!a->tile_counters) return fail(SDK_EINVAL, "conv2d: in-launch split-K needs tile_counters");
-    if (tiles > SDK_TILE_COUNTERS) return fail(SDK_EINVAL, "conv2d: in-launch split-K: more tiles than counters");
-    p.inl = 1;
-    p.tcnt = a->tile_counters;
-    ws = (int64_t)2 * tiles * tbm * tbn * 4;   // one fp32 accumulator blob per (tile, half)
-  }
-  if (info) {
-    info->split_k = split;
-    info->grid_tiles = tiles;
-    info->workspace_bytes = ws;
-    info->variant = var;
-    // the executed FLOPs: the phase form's K is 4 * cin over the same output pixels (padding rows not counted)
-    info->flops = 2.0 * (phase ? 4.0 * p.ph_rows : (double)p.M) * (double)p.N * kreal;
-  }
-  if (split > 1) {
-    if (a->cout % 8) return fail(SDK_EINVAL, "conv2d: split-K needs cout % 8 == 0 (pass split_k = 1)");
-    p.partial = a->workspace;
-  }
-  // GroupNorm statistics of the output: chunks per image the plan can emit (0 = none).  Split-K: the
-  // reduce kernel, 64-row chunks (one chunk when hw_out is not a multiple of 64); otherwise the
-  // LDS-DMA kernels' fp16 epilogue, one chunk per M-tile when tiles do not straddle images.
-  int gn_nch = 0;
-  if (a->out_mode == SDK_OUT_NHWC_F16) {
-    const int hw_img = (phase ? 4 : 1) * p.hw_out;   // output pixels of one image
-    if (split > 1 && !p.inl) gn_nch = hw_img % 64 == 0 ? hw_img / 64 : 1;
-    else if (emits_gn_stats(row) && p.hw_out % tbm == 0) gn_nch = hw_img / tbm;   // in-launch: the combining tile emits
-  }
-  if (info) info->gn_chunks = gn_nch;
-  if (a->gn_partial) {
-    if (gn_nch == 0)
-      return fail(SDK_EINVAL, "conv2d: this plan emits no GroupNorm statistics (sdk_conv_plan_info.gn_chunks == 0)");
-    p.gnp = reinterpret_cast<float2*>(a->gn_partial);
-    p.gn_nch = gn_nch;
-  }
-  return SDK_OK;
-}
-
-}  // namespace
-}  // namespace sdk
-
-using namespace sdk;
-
-extern "C" const char* sdk_kernel_name(int32_t variant) {
-  const Variant* r = variant_row(variant);
-  return r ? r->name : "unknown";
-}
-
-extern "C" int sdk_conv2d_plan(const sdk_conv_args* a, sdk_conv_plan_info* info) {
-  Params p;
-  return build_params(a, p, info);
-}
-
-extern "C" int sdk_conv2d(const sdk_conv_args* a, sdk_stream_t stream) {
-  Params p;
-  sdk_conv_plan_info info;
-  int rc = build_params(a, p, &info);
-  if (rc) return rc;
-  if (p.split > 1 && (!a->workspace || a->workspace_bytes < info.workspace_bytes))
-    return fail(SDK_EWORKSPACE, "conv2d: split-K workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(p.tiles_m * p.tiles_n, p.split);
-  const Variant& row = kVariants.row[p.variant];   // build_params plans ids of the table only
-  switch (row.fam) {
-    case Fam::IGEMM:
-      hipLaunchKernelGGL(conv_igemm_kernel, grid, dim3(NT), 0, s, p);
-      rc = check_launch("conv_igemm");
-      break;
-    case Fam::DIRECT: rc = launch_direct(p, s); break;
-    case Fam::SKINNY: rc = launch_skinny(p, s); break;
-    default:   // the tile kernels, each in its compile part (part 0 rows have no launcher: never planned)
-      rc = row.part ? kPartLaunch[row.part](p.variant, &p, (int)sizeof(Params), s)
-                    : fail(SDK_EINVAL, "conv2d: planned variant " + std::to_string(p.variant) + " has no kernel");
-  }
-  if (rc) return rc;
-  if (p.inl) return SDK_OK;   // combined inside the launch
-  if (p.split > 1 && p.gnp) {
-    hipLaunchKernelGGL(splitk_reduce_gn_kernel, dim3(p.batch * p.gn_nch, (p.N + 63) / 64), dim3(256), 0, s, p);
-    if (int e = check_launch("splitk_reduce_gn")) return e;
-  } else if (p.split > 1) {
-    const size_t total = (size_t)p.M * (p.N / 8);
-    int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, p);
-    if (int e = check_launch("splitk_reduce")) return e;
-  }
-  return SDK_OK;
-}
-
-#ifdef SDK_CONV_DIAGNOSTICS
-// diagnostics build only (not in include/sdk_amd.h): copy the phase stamps of the last stamped launches
-extern "C" int sdk_diag_conv_stamps(unsigned long long* host, long long n) {
-  if (!g_conv_stamps || n <= 0 || n > (long long)kStampWgs * 8) return SDK_EINVAL;
-  return hipMemcpy(host, g_conv_stamps, (size_t)n * 8, hipMemcpyDeviceToHost) == hipSuccess ? SDK_OK : SDK_EINVAL;
-}
-#endif
-#endif  // SDK_PART(0)

@@ -264,14 +264,26 @@ class PhaseConv:
         self.w_batch_stride = self.weight.shape[1] * self.weight.shape[2]
 
 
+def _conv_source_files():
+    """The conv sources and headers (csrc/conv*), sorted by name: what the tuning-cache key covers."""
+    import os
+    # SD_AMD_CONV_SOURCE: the csrc directory (or a file inside it) an A/B library (SD_AMD_LIB) was built from (tools only)
+    src = os.environ.get("SD_AMD_CONV_SOURCE") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
+    if not os.path.isdir(src):
+        src = os.path.dirname(src)
+    return [os.path.join(src, f) for f in sorted(os.listdir(src)) if f.startswith("conv")]
+
+
 def _conv_source_hash():
+    """sha1 over the name and bytes of every conv source file: any edit of one invalidates a tuning cache."""
     import hashlib
     import os
-    # SD_AMD_CONV_SOURCE: the conv.hip an A/B library (SD_AMD_LIB) was built from (tools only)
-    src = os.environ.get("SD_AMD_CONV_SOURCE") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc",
-                                                                "conv.hip")
-    with open(src, "rb") as f:
-        return hashlib.sha1(f.read()).hexdigest()[:16]
+    h = hashlib.sha1()
+    for path in _conv_source_files():
+        h.update(os.path.basename(path).encode() + b"\0")
+        with open(path, "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()[:16]
 
 
 class _Autotune:

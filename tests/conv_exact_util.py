@@ -20,7 +20,7 @@ OUT_NHWC_F16, OUT_NCHW_F32, OUT_GEGLU_F16, OUT_ROWS_F32 = 0, 1, 2, 3     # sdk_a
 # the ids of the `conv_variant` fixture (tests/test_gpu_kernels.py), re-declared
 VARIANT_IDS = ["auto", "0", "2", "3", "4", "6", "7", "8", "9", "16", "17", "18", "19", "20", "21", "22", "23", "24",
                "25", "26", "31", "32", "33", "38", "40"]
-# BM x BN of each tile variant, re-declared (csrc/conv.hip's variant table takes them from the config types;
+# BM x BN of each tile variant, re-declared (csrc/conv.h's variant table takes them from the config types;
 # tests/test_boundary.py checks this copy against the built library on the CPU)
 TILE = {0: (128, 128), 2: (256, 256), 3: (256, 128), 4: (128, 128), 6: (256, 160), 7: (128, 320), 8: (256, 256),
         9: (256, 256), 16: (128, 128), 17: (256, 128), 18: (128, 128), 19: (128, 256), 20: (256, 256),

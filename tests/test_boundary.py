@@ -118,7 +118,7 @@ def _gemm_args(_lib, M, N, K, out_mode=0):
 
 
 def test_hand_kept_variant_lists_agree_with_the_library(sdk):
-    """The lists that stay hand-kept outside csrc/conv.hip's variant table fail here when they drift from it:
+    """The lists that stay hand-kept outside csrc/conv.h's variant table fail here when they drift from it:
     the autotuner's candidates are the named ids minus the register-staged fallback and the retired 5; every
     id of the exact tests' re-declared TILE is honoured with that tile's grid, and under the GEGLU output
     exactly the ids of their GEGLU_OK are honoured."""
@@ -141,9 +141,35 @@ def test_hand_kept_variant_lists_agree_with_the_library(sdk):
 
 
 def test_committed_tuning_cache_matches_the_conv_source(sdk):
-    """configs/conv_tuning_mi355x.json is keyed by the hash of csrc/conv.hip: a stale key loads nothing."""
+    """configs/conv_tuning_mi355x.json is keyed by the hash of the csrc/conv* files: a stale key loads nothing."""
     from sd_amd import ops
     assert ops._Autotune().load(os.path.join(ROOT, "configs", "conv_tuning_mi355x.json")) > 0
+
+
+def test_conv_source_hash_covers_what_the_build_compiles(sdk, tmp_path, monkeypatch):
+    """The tuning-cache key reads exactly the conv sources and headers the build compiles or lists as dependencies
+    of the conv units, and one changed byte in any of them changes the key."""
+    import shutil
+    from sd_amd import build, ops
+    built = set()
+    for src, _stem, _defs in build._units():
+        if src.startswith("conv"):
+            built |= {os.path.basename(d) for d in build._deps(src, build.CSRC) if os.path.basename(d).startswith("conv")}
+    hashed = [os.path.basename(f) for f in ops._conv_source_files()]
+    assert len(hashed) >= 5 and set(hashed) == built and hashed == sorted(built)
+    copy = tmp_path / "csrc"
+    shutil.copytree(build.CSRC, copy)
+    want = ops._conv_source_hash()
+    monkeypatch.setenv("SD_AMD_CONV_SOURCE", str(copy))
+    assert ops._conv_source_hash() == want
+    monkeypatch.setenv("SD_AMD_CONV_SOURCE", str(copy / hashed[0]))   # a file inside the directory names it too
+    assert ops._conv_source_hash() == want
+    for name in hashed:
+        data = (copy / name).read_bytes()
+        (copy / name).write_bytes(data[:-1] + bytes([data[-1] ^ 1]))
+        assert ops._conv_source_hash() != want, name
+        (copy / name).write_bytes(data)
+    assert ops._conv_source_hash() == want
 
 
 def test_group_norm_workspace(sdk):

@@ -48,7 +48,7 @@ def test_tuning_table_matches_kernel_source(bench_c3):
     """The committed tuning table was measured on the current conv kernel source (else the bench
     would run untuned choices) and covers every conv problem of the C3 UNet step."""
     from sd_amd import ops
-    assert bench_c3["loaded"] > 0, "configs/conv_tuning_mi355x.json is stale for csrc/conv.hip: re-tune"
+    assert bench_c3["loaded"] > 0, "configs/conv_tuning_mi355x.json is stale for the csrc/conv* sources: re-tune"
     ld, xT, ctx = bench_c3["ld"], bench_c3["xT"], bench_c3["ctx"]
     missing = []
     orig = ops.AUTOTUNE.choose

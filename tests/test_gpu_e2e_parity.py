@@ -51,7 +51,7 @@ def _bench_models(name):
     cfg = bench.CONFIGS[name]
     ops.AUTOTUNE.table.clear()
     loaded = ops.AUTOTUNE.load(os.path.join(ROOT, "configs", "conv_tuning_mi355x.json"))
-    assert loaded > 0, "the committed tuning table is stale for csrc/conv.hip"
+    assert loaded > 0, "the committed tuning table is stale for the csrc/conv* sources"
     ops.AUTOTUNE.enable(False)
     unet, vae, ld = bench.build_models(cfg, DEV, graph=True)
     B, L = cfg["batch"], cfg["latent"]

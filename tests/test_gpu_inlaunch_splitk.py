@@ -1,4 +1,4 @@
-"""In-launch split-K of the LDS-DMA conv / GEMM kernels (sdk_conv_args.split_inlaunch, conv.hip
+"""In-launch split-K of the LDS-DMA conv / GEMM kernels (sdk_conv_args.split_inlaunch, conv_tile.h
 conv_glds_kernel): the two K halves of a tile combine inside the launch — the second workgroup to arrive adds
 the first's fp32 accumulator blob and runs the whole epilogue — instead of fp32 slabs + splitk_reduce.  The
 combine adds the same two partial sums in the same order as the slab reduce, so the outputs are bitwise the

@@ -1,4 +1,4 @@
-"""Tile visiting order of unsplit conv plans (sdk_conv_args.tile_group_m, conv.hip item_coords): the order
+"""Tile visiting order of unsplit conv plans (sdk_conv_args.tile_group_m, conv_tile.h item_coords): the order
 only changes which workgroup computes which tile, so every grouping — M-panel major, groups of 8 / 16
 panels, and a group size that leaves a short last group — gives bitwise the same output, GroupNorm
 statistics included.  Shapes: the 32² GEGLU FF1 GEMM (reference openai_model/attention.py:129-141) and a 64²

@@ -16,7 +16,7 @@ from gpu_util import rel_l2
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
-# the LDS-DMA tile variants whose linear-issue kernel carries the phase form (csrc/conv.hip: the GLDS family of the variant table)
+# the LDS-DMA tile variants whose linear-issue kernel carries the phase form (csrc/conv.h: the GLDS family of the variant table)
 ADMITTED = (2, 3, 4, 6, 7, 16, 17, 18, 19, 22, 23, 24, 25, 26, 31, 32, 33, 38, 40)
 REFUSED = (0, 8, 9, 20, 21)        # register-staged and phased kernels: the planner picks an admitted one
 B, H, W = 3, 7, 6                  # 126 rows per phase: ragged in every M-tile, tiles cross images

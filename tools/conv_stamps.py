@@ -1,6 +1,6 @@
 """Phase times of one conv configuration from the diagnostics build's workgroup stamps (SDK_CONV_STAMPS=1,
 libsdk_amd_diag.so): per workgroup, thread 0's s_memtime at entry / after the prologue / after the K loop /
-at the end (conv.hip ph_stamp).  Prints the mean cycles of prologue, K loop and epilogue, the mean workgroup
+at the end (conv_device.h ph_stamp).  Prints the mean cycles of prologue, K loop and epilogue, the mean workgroup
 lifetime, and the kernel span in cycles.
 usage: SD_AMD_LIB=.../libsdk_amd_diag.so SDK_CONV_STAMPS=1 python tools/conv_stamps.py <shape> <variant>"""
 import ctypes, os, sys
