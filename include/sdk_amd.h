@@ -275,19 +275,50 @@ int sdk_attention(const sdk_attention_args* a, sdk_stream_t stream);
  *   SDK_ATTN_NW8_STAG  8 waves, waves 4..7 run half a key tile behind waves 0..3 (three LDS stages);
  *                      head_dim 40..80
  *   SDK_ATTN_QB2       4 waves with two 32-row query blocks each; head_dim 40..48, non-causal
+ *   SDK_ATTN_WIDE      head_dim 168..512 (AUTO's choice above 160), non-causal: the 8 waves of a workgroup
+ *                      share SDK_ATTN_WIDE_ROWS = 64 query rows, staged once in LDS, compute each
+ *                      SDK_ATTN_WIDE_KT = 32-key score tile once and split head_dim between them for
+ *                      O += P V (the first stage's one-head AttnBlock, C = 512).  Instantiated for padded
+ *                      head dims 256 (head_dim <= 256) and 512.  At head_dim <= 160, or with causal,
+ *                      SDK_EINVAL
  * A form other than AUTO that has no instantiation at a->head_dim (or QB2 with a->causal) returns
  * SDK_EINVAL; it never falls back to another form.
  * ran (may be NULL) receives what was launched, from the launched kernel's template arguments: form (the
  * form after AUTO is resolved), dqk / dv (the padded head dim of the QK^T and the PV products), waves per
- * workgroup, qblocks (32-row query blocks per wave), stagger, seed_col (head_dim 40 with 8 waves: the
+ * workgroup, qblocks (32-row query blocks per wave; under SDK_ATTN_WIDE the 32-row query blocks per
+ * WORKGROUP, SDK_ATTN_WIDE_ROWS / 32 = 2, which all its waves share: grid = ceil(nq / 64) * heads * batch), stagger, seed_col (head_dim 40 with 8 waves: the
  * padding column of Q that carries the running max; else 0), causal and grid (workgroups).  The causal
  * kernels are neither staggered nor seeded through a column, so a causal launch reports stagger = 0 and
  * seed_col = 0 under every form.  ran is written on the host before the launch: it costs nothing and is
  * the same under stream capture. */
-enum { SDK_ATTN_AUTO = 0, SDK_ATTN_NW4, SDK_ATTN_NW8, SDK_ATTN_NW8_STAG, SDK_ATTN_QB2 };
+enum { SDK_ATTN_AUTO = 0, SDK_ATTN_NW4, SDK_ATTN_NW8, SDK_ATTN_NW8_STAG, SDK_ATTN_QB2, SDK_ATTN_WIDE };
+#define SDK_ATTN_WIDE_ROWS 64   /* query rows per workgroup of SDK_ATTN_WIDE */
+#define SDK_ATTN_WIDE_KT 32     /* keys per tile of SDK_ATTN_WIDE (two-slot K / V ring) */
 typedef struct { int32_t form, dqk, dv, waves, qblocks, stagger, seed_col, causal, grid; } sdk_attention_form_info;
 int sdk_attention_form(const sdk_attention_args* a, int32_t form, sdk_attention_form_info* ran /* may be NULL */,
                        sdk_stream_t stream);
+
+/* Linear attention (Unet/attention.py:131-181, LinearAttention.forward after to_qkv), per (batch, head):
+ *   ctx[d][e] = sum_n softmax_n(k)[n][d] * v[n][e],   out[n][e] = sum_d q[n][d] * ctx[d][e]
+ * q / k / v / o: 2-D fp16 views [batch*n, ld], head h at columns h*dim_head.. (as sdk_attention).
+ * dim_head: a multiple of 8 in [8, 512]; any heads.  No scale and no softmax over q (the reference has neither).
+ * Three launches, no floating-point atomics, a fixed summation order (bitwise reproducible):
+ *  1. context: the tokens are cut into sdk_linear_attention_chunks(n) chunks; per chunk and column d the
+ *     maximum m_c[d] of k*log2(e), P = exp2(k*log2(e) - m_c) rounded to fp16, ctx_c = P^T V by MFMA into fp32,
+ *     den_c = the column sums of P (fp32, before rounding); (m_c, den_c, ctx_c) go to the workspace;
+ *  2. combine: the chunks in ascending order, each weighted by exp2(m_c - max_c m_c); ctx / den, rounded to
+ *     fp16, stored transposed ([e][d]) in the workspace;
+ *  3. apply: out = q ctx, an MFMA GEMM whose B operand is per (batch, head).
+ * workspace: sdk_linear_attention_workspace_bytes(a) bytes, 16-B aligned. */
+typedef struct {
+  const void* q; const void* k; const void* v; void* o;
+  int32_t q_ld, k_ld, v_ld, o_ld;
+  int32_t batch, heads, n, dim_head;
+  void* workspace; int64_t workspace_bytes;
+} sdk_linear_attention_args;
+int32_t sdk_linear_attention_chunks(int32_t n);
+int64_t sdk_linear_attention_workspace_bytes(const sdk_linear_attention_args* a);
+int sdk_linear_attention(const sdk_linear_attention_args* a, sdk_stream_t stream);
 
 /* Fused cross-attention block on a cached context K|V: out = (softmax(scale * (t Wq^T)_h K_h^T) V_h)_h
  * Wo^T + bias + res, one kernel, q and o kept in LDS.  Replaces, per denoising step, the

@@ -59,6 +59,12 @@ class AttentionFormInfo(C.Structure):
                 ("seed_col", i32), ("causal", i32), ("grid", i32)]
 
 
+class LinearAttentionArgs(C.Structure):
+    _fields_ = [("q", vp), ("k", vp), ("v", vp), ("o", vp), ("q_ld", i32), ("k_ld", i32), ("v_ld", i32),
+                ("o_ld", i32), ("batch", i32), ("heads", i32), ("n", i32), ("dim_head", i32), ("workspace", vp),
+                ("workspace_bytes", i64)]
+
+
 class XAttnArgs(C.Structure):
     _fields_ = [("t", vp), ("kv", vp), ("wq", vp), ("wo", vp), ("bias", vp), ("res", vp), ("out", vp),
                 ("t_ld", i32), ("kv_ld", i32), ("w_ld", i32), ("res_ld", i32), ("out_ld", i32), ("batch", i32),
@@ -125,13 +131,14 @@ class Resize2dArgs(C.Structure):
 OUT_NHWC_F16, OUT_NCHW_F32, OUT_GEGLU_F16, OUT_ROWS_F32 = 0, 1, 2, 3
 RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_BICUBIC, RESIZE_AREA = range(4)
 ACT_NONE, ACT_QUICK_GELU = 0, 1
-ATTN_AUTO, ATTN_NW4, ATTN_NW8, ATTN_NW8_STAG, ATTN_QB2 = range(5)
+ATTN_AUTO, ATTN_NW4, ATTN_NW8, ATTN_NW8_STAG, ATTN_QB2, ATTN_WIDE = range(6)
+ATTN_WIDE_ROWS, ATTN_WIDE_KT = 64, 32      # SDK_ATTN_WIDE_ROWS / SDK_ATTN_WIDE_KT
 RESAMPLE_AVGPOOL2, RESAMPLE_NEAREST2 = 0, 1
 GN_STATS = ("given", "slice", "chunked", "parts")              # SDK_GN_STATS_*
 GN_APPLY = ("none", "in_stats", "flat", "row", "stride")       # SDK_GN_APPLY_*
 
 EXPORTS = ["sdk_conv2d_plan", "sdk_conv2d", "sdk_group_norm_workspace", "sdk_group_norm_affine", "sdk_group_norm_apply", "sdk_group_norm_apply_padded", "sdk_group_norm_apply_ex", "sdk_group_norm", "sdk_group_norm_finalize", "sdk_group_norm_plan", "sdk_layer_norm",
-           "sdk_attention", "sdk_attention_form", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_ddim_step_ex", "sdk_cfg_combine", "sdk_posterior_step", "sdk_posterior_step_ex", "sdk_masked_q_sample", "sdk_concat_nchw_to_nhwc", "sdk_patch_pack", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
+           "sdk_attention", "sdk_attention_form", "sdk_linear_attention", "sdk_linear_attention_workspace_bytes", "sdk_linear_attention_chunks", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_ddim_step_ex", "sdk_cfg_combine", "sdk_posterior_step", "sdk_posterior_step_ex", "sdk_masked_q_sample", "sdk_concat_nchw_to_nhwc", "sdk_patch_pack", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
            "sdk_diag_gaussian_sample", "sdk_stochastic_encode", "sdk_token_embedding", "sdk_extract_patches",
            "sdk_fold_patches", "sdk_vq_code_norms", "sdk_vq_nearest_splits", "sdk_vq_nearest", "sdk_vq_lookup", "sdk_vq_remap",
            "sdk_upsample_bilinear2x", "sdk_upsample_nearest2x_padded", "sdk_zero_border", "sdk_gelu",
@@ -177,6 +184,11 @@ def lib():
     L.sdk_layer_norm.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, f32, vp]
     L.sdk_attention.argtypes = [C.POINTER(AttentionArgs), vp]
     L.sdk_attention_form.argtypes = [C.POINTER(AttentionArgs), i32, C.POINTER(AttentionFormInfo), vp]
+    L.sdk_linear_attention.argtypes = [C.POINTER(LinearAttentionArgs), vp]
+    L.sdk_linear_attention_workspace_bytes.argtypes = [C.POINTER(LinearAttentionArgs)]
+    L.sdk_linear_attention_workspace_bytes.restype = i64
+    L.sdk_linear_attention_chunks.argtypes = [i32]
+    L.sdk_linear_attention_chunks.restype = i32
     L.sdk_cross_attention_block_supported.argtypes = [i32, i32, i32, i32]
     L.sdk_xattn_pack_weight.argtypes = [vp, i32, vp, i32, vp]
     L.sdk_cross_attention_block.argtypes = [C.POINTER(XAttnArgs), vp]

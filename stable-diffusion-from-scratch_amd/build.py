@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsdk_amd.so")
-SOURCES = ["norm.hip", "attention.hip", "sampler.hip", "xattn.hip", "ff.hip", "token.hip", "vq.hip", "cond.hip", "probe.hip"]
+SOURCES = ["norm.hip", "attention.hip", "attention_wide.hip", "linattn.hip", "sampler.hip", "xattn.hip", "ff.hip", "token.hip", "vq.hip", "cond.hip", "probe.hip"]
 # the conv units: the host planner, the small kernels, and the tile kernels, whose one small source is compiled
 # once per part (-DSDK_CONV_PART=k expands the launcher of that part's variant rows) so the objects build in parallel
 CONV_TILE_PARTS = 5
@@ -36,7 +36,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result"]
 # attention: IEEE mode off + no NaN semantics, so fmaxf on MFMA results is one v_max3 instead of
 # canonicalising v_max x,x copies first (the inputs are finite fp16 products)
-EXTRA = {"attention.hip": ["-mno-amdgpu-ieee", "-fno-honor-nans"]}
+EXTRA = {"attention.hip": ["-mno-amdgpu-ieee", "-fno-honor-nans"],
+         "attention_wide.hip": ["-mno-amdgpu-ieee", "-fno-honor-nans"]}
 # every kernel's register / scratch use is recorded from the compiler's resource remarks
 # (build*/resource_usage.txt).  The token linear's ring immediates count its own global stores
 # (token.hip: D + 2 * (TL_CPT + 10)), so a scratch spill or a split store there could retire a ring slot
@@ -44,7 +45,9 @@ EXTRA = {"attention.hip": ["-mno-amdgpu-ieee", "-fno-honor-nans"]}
 # kernels a spill only over-waits (an extra VMEM op never lowers the count of the DMAs a wait covers), so
 # it is reported as a warning (it costs time: scratch round trips in the K loop)
 REMARK = "-Rpass-analysis=kernel-resource-usage"
-NO_SCRATCH = re.compile(r"token_linear320_kernel")
+# the wide attention kernel (attention_wide.hip) sits at 168 VGPRs with one workgroup per CU: a spill would put
+# scratch round trips into every 32-key tile, so it must build without scratch too
+NO_SCRATCH = re.compile(r"token_linear320_kernel|attn_wide_kernel")
 WARN_SCRATCH = re.compile(r"conv_glds_kernel|conv_ph_kernel|ff_geglu_kernel|xattn_block_kernel|attn_fwd_kernel|vq_nearest_")
 _RES = re.compile(r"remark: (?:Function Name: (\S+)|\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+))")
 

@@ -439,6 +439,7 @@ int auto_form(int d) {
   // profiles/r3_attn_stag_ab.txt; d = 80 at SD-1's 32x32 level 67.1-67.5 vs 69.3 us, profiles/r5_attn80_ab.txt);
   // SDK_ATTN_STAG=0 / 1 forces it off / on everywhere
   static const int stag_env = getenv("SDK_ATTN_STAG") ? atoi(getenv("SDK_ATTN_STAG")) : -1;
+  if (d > 160) return SDK_ATTN_WIDE;
   if (d <= 32 || d > 80) return SDK_ATTN_NW4;
   if (d <= 48 && qb2) return SDK_ATTN_QB2;
   if (nw4) return SDK_ATTN_NW4;
@@ -458,8 +459,8 @@ extern "C" int sdk_attention(const sdk_attention_args* a, sdk_stream_t stream) {
 extern "C" int sdk_attention_form(const sdk_attention_args* a, int32_t form, sdk_attention_form_info* ran,
                                   sdk_stream_t stream) {
   if (!a || !a->q || !a->k || !a->v || !a->o) return fail(SDK_EINVAL, "attention: null pointer");
-  if (a->head_dim <= 0 || a->head_dim % 8 || a->head_dim > 160)
-    return fail(SDK_EINVAL, "attention: head_dim must be a multiple of 8 in [8, 160]");
+  if (a->head_dim <= 0 || a->head_dim % 8 || a->head_dim > 512)
+    return fail(SDK_EINVAL, "attention: head_dim must be a multiple of 8 in [8, 512]");
   if (a->q_ld % 8 || a->k_ld % 8 || a->v_ld % 8 || a->o_ld % 4)
     return fail(SDK_EINVAL, "attention: row strides must be multiples of 8 (o: 4)");
   if (a->nk <= 0 || a->nq <= 0 || a->batch <= 0 || a->heads <= 0) return fail(SDK_EINVAL, "attention: empty");
@@ -472,13 +473,15 @@ extern "C" int sdk_attention_form(const sdk_attention_args* a, int32_t form, sdk
                a->scale * 1.4426950408889634f, a->causal ? 1 : 0};
   hipStream_t s = (hipStream_t)stream;
   const int d = a->head_dim;
-  if (form < SDK_ATTN_AUTO || form > SDK_ATTN_QB2) return fail(SDK_EINVAL, "attention: unknown form");
+  if (form < SDK_ATTN_AUTO || form > SDK_ATTN_WIDE) return fail(SDK_EINVAL, "attention: unknown form");
   const int f = form == SDK_ATTN_AUTO ? auto_form(d) : form;
+  // one head too wide for a wave's registers: the workgroup-shared kernel of attention_wide.hip
+  if (f == SDK_ATTN_WIDE && d > 160) return attention_wide(a, s, ran);
   for (const AttnInst& e : ATTN_TABLE)
     if (e.form == f && d >= e.dmin && d <= e.dmax) {
       if (ran) ran->form = f;
       return e.run(p, s, ran);
     }
   return fail(SDK_EINVAL, "attention: this form has no instantiation at this head_dim (8 waves and the staggered "
-                          "form: 40..80; two blocks per wave: 40..48)");
+                          "form: 40..80; two blocks per wave: 40..48; wide: 168..512, the others: up to 160)");
 }

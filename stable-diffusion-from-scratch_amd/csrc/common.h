@@ -21,6 +21,8 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 void set_error(const std::string& msg);
 int fail(int code, const std::string& msg);
 int check_launch(const char* what);
+// attention_wide.hip: the SDK_ATTN_WIDE launch behind sdk_attention_form (arguments already validated)
+int attention_wide(const sdk_attention_args* a, hipStream_t s, sdk_attention_form_info* ran);
 
 // Raise a kernel's dynamic-LDS cap on the CURRENT device.  hipFuncSetAttribute is per device, so
 // the "already done" state is one bit per device id (a process that drives a second GPU sets it

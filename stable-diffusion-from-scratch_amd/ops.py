@@ -1045,14 +1045,19 @@ def probe_peaks(reps=3):
 # --------------------------------------------------------------------------- attention
 
 ATTN_FORMS = {"auto": _lib.ATTN_AUTO, "nw4": _lib.ATTN_NW4, "nw8": _lib.ATTN_NW8, "nw8_stag": _lib.ATTN_NW8_STAG,
-              "qb2": _lib.ATTN_QB2}
+              "qb2": _lib.ATTN_QB2, "wide": _lib.ATTN_WIDE}
 _ATTN_FORM_NAMES = {v: k for k, v in ATTN_FORMS.items()}
+# the wide form (head_dim 168..512): query rows per workgroup (grid = ceil(nq / ROWS) * heads * batch) and keys
+# per tile of its two-slot K / V ring
+ATTN_WIDE_ROWS = _lib.ATTN_WIDE_ROWS
+ATTN_WIDE_KT = _lib.ATTN_WIDE_KT
 
 
 def attention(q, k, v, *, batch, heads, nq, nk, head_dim, scale, out=None, causal=False, form=None, form_out=None):
     """q/k/v: 2-D fp16 views [batch*n, ld] (head h at columns h*head_dim...); ``causal`` masks
     key j > query i.  ``form``: None / "auto" (the head dim's default) or "nw4" / "nw8" / "nw8_stag" /
-    "qb2" (``sdk_attention_form``; a form without an instantiation at this head dim raises).
+    "qb2" / "wide" (``sdk_attention_form``; a form without an instantiation at this head dim raises;
+    "wide" is head_dim 168..512, non-causal, and what "auto" runs above 160).
     ``form_out``: a dict that receives the launched kernel's form and template arguments (host
     integers, filled before the launch; the same under graph capture)."""
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
@@ -1076,6 +1081,32 @@ def attention(q, k, v, *, batch, heads, nq, nk, head_dim, scale, out=None, causa
             form_out.update(form=_ATTN_FORM_NAMES[info.form], dqk=info.dqk, dv=info.dv, waves=info.waves,
                             qblocks=info.qblocks, stagger=info.stagger, seed_col=info.seed_col,
                             causal=info.causal, grid=info.grid)
+    if PROFILER.active:
+        PROFILER.end()
+    return out
+
+
+def linear_attention(q, k, v, *, batch, heads, n, dim_head, out=None):
+    """Linear attention (``sdk_linear_attention``): per (batch, head) ``ctx = softmax_n(k)^T v`` then
+    ``out = q ctx``.  q/k/v: 2-D fp16 views [batch*n, ld], head h at columns h*dim_head...; dim_head a
+    multiple of 8 in [8, 512].  The workspace (chunk partials and the fp16 context) is allocated here."""
+    for t, nm in ((q, "q"), (k, "k"), (v, "v")):
+        _need_cuda(t, "linear_attention " + nm)
+    if out is None:
+        out = torch.empty(batch * n, heads * dim_head, dtype=torch.float16, device=q.device)
+    _claim(out)
+    a = _lib.LinearAttentionArgs()
+    a.q, a.k, a.v, a.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    a.q_ld, a.k_ld, a.v_ld, a.o_ld = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
+    a.batch, a.heads, a.n, a.dim_head = batch, heads, n, dim_head
+    nbytes = lib().sdk_linear_attention_workspace_bytes(C.byref(a))
+    if nbytes < 0:
+        check(-1, "linear_attention")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    if PROFILER.active:
+        PROFILER.begin("linear_attention", None)
+    check(lib().sdk_linear_attention(C.byref(a), _stream()), "linear_attention")
     if PROFILER.active:
         PROFILER.end()
     return out
