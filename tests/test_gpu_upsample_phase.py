@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_exact_util as U
+import gn_stats_exact_util as GS
 from gpu_util import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -135,31 +136,36 @@ def test_phase_conv_rejects_what_it_cannot_do(ops):
         ops.conv2d(c.ppc, c.xpad, phase=True, residual=torch.zeros(c.out_shape, dtype=torch.float16, device=DEV))
 
 
-def _phase_major(y):
-    """[B, 2H, 2W, C] -> [B, 4 * H * W, C], an image's pixels in the form's chunk order (phase major)."""
-    b, h2, w2, ch = y.shape
-    return y.reshape(b, h2 // 2, 2, w2 // 2, 2, ch).permute(0, 2, 4, 1, 3, 5).reshape(b, h2 * w2, ch)
-
-
 def _check_partials(ops, c, y, plan):
     part = getattr(y, ops.GN_ATTR, None)
     assert part is not None and plan["gn_chunks"] > 0, f"plan {plan} should emit GroupNorm statistics"
     pp, nch, _ = part
     rows = 4 * c.h * c.w_
     assert pp.shape == (c.b, nch, c.n, 2) and nch == plan["gn_chunks"] and rows % nch == 0
-    t = _phase_major(y).double().reshape(c.b, nch, rows // nch, c.n)
+    # every (image, chunk, channel) pair against the float64 statistics of exactly that chunk's stored rows, phase
+    # major (a swapped chunk leaves every merged statistic unchanged), under the operation-count bound of the route
+    # that emitted (tests/gn_stats_exact_util.py): the split-K reduce's 32 row lanes, else the tile's row blocks
+    s = GS.REDUCE_S if plan["split_k"] > 1 else GS.tile_s(U.TILE[plan["variant"]][0])
+    GS.check_chunk_stats(pp, y, s, phase=True, what=f"{c.name} plan {plan}")
+    # the tolerances of test_conv_emits_group_norm_statistics stay: at these magnitudes (|y| up to 100) they are the
+    # tighter ones for the mean
+    t = GS.phase_major(y).double().reshape(c.b, nch, rows // nch, c.n)
     mean = t.mean(2)
     m2 = ((t - mean[:, :, None]) ** 2).sum(2)
-    # the tolerances of test_conv_emits_group_norm_statistics
     assert torch.allclose(pp[..., 0].double().cpu(), mean.cpu(), rtol=1e-5, atol=1e-4)
     assert rel_l2(pp[..., 1].double().cpu(), m2.cpu()) < 1e-4
     if c.n % 32 == 0:      # finalized: GroupNorm from the partials == GroupNorm from its own statistics pass
         g = torch.Generator().manual_seed(7)
-        gamma = (torch.rand(c.n, generator=g) + 0.5).to(DEV)
-        beta = (torch.randn(c.n, generator=g) * 0.1).to(DEV)
-        s1 = ops.group_norm_scale_shift(y, gamma, beta, 1e-5, 32)
-        s0 = ops.group_norm_scale_shift(y.clone(), gamma, beta, 1e-5, 32)
+        gamma = torch.rand(c.n, generator=g) + 0.5
+        beta = torch.randn(c.n, generator=g) * 0.1
+        s1 = ops.group_norm_scale_shift(y, gamma.to(DEV), beta.to(DEV), 1e-5, 32)
+        s0 = ops.group_norm_scale_shift(y.clone(), gamma.to(DEV), beta.to(DEV), 1e-5, 32)
         assert rel_l2(s1[0], s0[0]) < 1e-3 and rel_l2(s1[1], s0[1]) < 1e-3
+        # ... and within the three-rounding bounds of the float64 merge of the same fp32 partials
+        ref = GS.Affine(*GS.merge_partials([pp.cpu()], rows, 32), 1e-5, gamma, beta, c.n // 32,
+                        amax=y.abs().max().item())
+        rs, rh = ref.ratios(*s1)
+        assert rs <= 1.0 and rh <= 1.0, f"{c.name}: finalize of the emitted partials off by {rs:.3g} / {rh:.3g} of the bound"
 
 
 @pytest.mark.parametrize("split", [2, 3])
