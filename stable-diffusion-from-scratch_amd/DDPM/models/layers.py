@@ -23,15 +23,7 @@ import torch
 from torch import nn
 
 from ... import ops
-
-
-def _gn_prep(gn, dev):
-    gn._g = gn.weight.detach().to(dev, torch.float32).contiguous()
-    gn._b = gn.bias.detach().to(dev, torch.float32).contiguous()
-
-
-def _stats(gn, x):
-    return ops.group_norm_affine(x, gn._g, gn._b, gn.eps, gn.num_groups)
+from ...packing import gn_affine, prep_norm
 
 
 class TransformerPositionalEmbedding(nn.Module):
@@ -65,11 +57,11 @@ class ConvBlock(nn.Module):
 
     def _prepare(self, dev, cin_src=None):
         self._pc = ops.PackedConv([(self.conv.weight, cin_src or self.conv.in_channels)], self.conv.bias, device=dev)
-        _gn_prep(self.norm, dev)
+        prep_norm(self.norm, dev)
 
     def _run(self, x, post_bias=None, residual=None):
         h = ops.conv2d(self._pc, x)
-        return ops.group_norm_apply_ex(h, _stats(self.norm, h), silu=True, post_bias=post_bias, residual=residual)
+        return ops.group_norm_apply_ex(h, gn_affine(self.norm, h), silu=True, post_bias=post_bias, residual=residual)
 
 
 class DownsampleBlock(nn.Module):
@@ -142,7 +134,7 @@ class SelfAttentionBlock(nn.Module):
         self._pc_qkv = ops.PackedConv([(w, self.query_projection.in_features)], b, device=dev)
         self._pc_o = ops.PackedConv([(self.final_projection.weight, self.d_model)], self.final_projection.bias,
                                     device=dev)
-        _gn_prep(self.norm, dev)
+        prep_norm(self.norm, dev)
 
     def _run(self, x):
         B, H, W, Cc = x.shape
@@ -153,7 +145,7 @@ class SelfAttentionBlock(nn.Module):
         o = ops.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], batch=B, heads=self.num_heads, nq=H * W,
                           nk=H * W, head_dim=self.d_keys, scale=self.d_keys ** -0.5)
         p = ops.linear(self._pc_o, o, residual=tok).view(B, H, W, Cc)
-        return ops.group_norm_apply_ex(p, _stats(self.norm, p), silu=False)
+        return ops.group_norm_apply_ex(p, gn_affine(self.norm, p), silu=False)
 
 
 class _Block(nn.Module):

@@ -12,11 +12,12 @@ import torch
 from torch import nn
 
 from ... import ops
+from ...packing import PackedOwner, gn_affine, prep_norm
 from .layers import (AttentionDownBlock, AttentionUpBlock, ConvDownBlock, ConvUpBlock, ResNetBlock,
-                     TransformerPositionalEmbedding, _gn_prep)
+                     TransformerPositionalEmbedding)
 
 
-class UNet(nn.Module):
+class UNet(PackedOwner, nn.Module):
     def __init__(self, image_size=256, input_channels=3):
         super().__init__()
         self.input_channels = input_channels
@@ -46,14 +47,8 @@ class UNet(nn.Module):
                         time_emb_channels=128 * 4)])
         self.output_conv = nn.Sequential(nn.GroupNorm(num_channels=256, num_groups=32), nn.SiLU(),
                                          nn.Conv2d(256, 3, 3, padding=1))
-        self._prepared_on = None
 
-    def load_state_dict(self, *args, **kwargs):
-        self._prepared_on = None
-        return super().load_state_dict(*args, **kwargs)
-
-    @torch.no_grad()
-    def _prepare(self, dev):
+    def _pack(self, dev):
         self._cin_pad = (self.input_channels + 7) // 8 * 8
         self._pc_in = ops.PackedConv([(self.initial_conv.weight, self._cin_pad)], self.initial_conv.bias, device=dev)
         pe, l1, _, l2 = self.positional_encoding
@@ -74,18 +69,15 @@ class UNet(nn.Module):
                 m._prepare(dev)
         # every ResNetBlock's Linear(SiLU(temb)) in one GEMM (A-side SiLU, fp32 rows [B, sum(out)])
         self._pc_emb = ops.PackedConv([(torch.cat(ws, 0), 512)], torch.cat(bs, 0), device=dev)
-        gn = self.output_conv[0]
-        _gn_prep(gn, dev)
+        prep_norm(self.output_conv[0], dev)
         conv = self.output_conv[2]
         self._pc_out = ops.PackedConv([(conv.weight, 256)], conv.bias, device=dev)
-        self._prepared_on = dev
 
     @torch.no_grad()
     def forward(self, input_tensor, time):
         if not input_tensor.is_cuda:
             raise TypeError("sd_amd.DDPM UNet: HIP path only — move inputs to the GPU")
-        if self._prepared_on != input_tensor.device:
-            self._prepare(input_tensor.device)
+        self.ensure_packed(input_tensor.device)
         B = input_tensor.shape[0]
         t = torch.as_tensor(time, device=input_tensor.device).to(torch.int64).reshape(-1)
         if t.numel() == 1 and B > 1:
@@ -103,7 +95,6 @@ class UNet(nn.Module):
         x = self.bottleneck._run(x, emb_all)
         for blk, skip in zip(self.upsample_blocks, skips):
             x = blk._run((x, skip), emb_all)
-        gn = self.output_conv[0]
         src = (x, skips[-1])
-        xa = ops.group_norm_apply(src, ops.group_norm_affine(src, gn._g, gn._b, gn.eps, gn.num_groups), silu=True)
+        xa = ops.group_norm_apply(src, gn_affine(self.output_conv[0], src), silu=True)
         return ops.conv2d(self._pc_out, xa, out_mode=ops.OUT_NCHW_F32)

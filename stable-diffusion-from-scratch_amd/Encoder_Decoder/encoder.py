@@ -18,11 +18,18 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..packing import PackedOwner, gn_norm, prep_norm
 from ..Unet.attention import make_attention
-from ..Unet.unet import Downsample, Normalize, ResnetBlock, Upsample, _gn_prep, gn_act
+from ..Unet.unet import Downsample, Normalize, ResnetBlock, Upsample
 
 
-class Encoder(nn.Module):
+def _prepare_blocks(owner, dev):
+    for m in owner.modules():
+        if m is not owner and hasattr(m, "_prepare"):
+            m._prepare(dev)
+
+
+class Encoder(PackedOwner, nn.Module):
     def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions, dropout=0.0,
                  resamp_with_conv=True, in_channels, resolution, z_channels, double_z=True, use_linear_attn=False,
                  attn_type="vanilla", **ignore_kwargs):
@@ -70,22 +77,21 @@ class Encoder(nn.Module):
 
         self._block_out = block_in
 
-    def _prepare(self, dev, in_pad, quant_conv=None):
-        """Pack every conv; conv_out is folded with ``quant_conv`` (1x1) when given:
-        W = Wq·Wout, b = Wq·b_out + b_q (fp32 on the host, then fp16)."""
+    def _pack(self, dev, in_pad, folded, quant_conv=None):
+        """Pack every conv for the key (device, input channel padding, ``quant_conv`` folded); when folded, conv_out
+        is composed with the owner's ``quant_conv`` (1x1): W = Wq·Wout, b = Wq·b_out + b_q (fp32 on the host, then
+        fp16)."""
+        assert folded == (quant_conv is not None)
         self._in_pad = in_pad
         self._pc_in = ops.PackedConv([(self.conv_in.weight, in_pad)], self.conv_in.bias, device=dev)
-        for m in self.modules():
-            if m is not self and hasattr(m, "_prepare") and not isinstance(m, (Encoder, Decoder)):
-                m._prepare(dev)
-        _gn_prep(self.norm_out, dev)
+        _prepare_blocks(self, dev)
+        prep_norm(self.norm_out, dev)
         w, b = self.conv_out.weight.detach().float(), self.conv_out.bias.detach().float()
-        if quant_conv is not None:
+        if folded:
             wq = quant_conv.weight.detach().float()[:, :, 0, 0]
             w = torch.einsum("nj,jcyx->ncyx", wq, w)
             b = wq @ b + quant_conv.bias.detach().float()
         self._pc_out = ops.PackedConv([(w, self._block_out)], b, device=dev)
-        self._prepared_on = (dev, in_pad, quant_conv is not None)
 
     def _run(self, x_nhwc):
         """x_nhwc: fp16 [B, H, W, in_pad] → fp32 NCHW conv_out (∘ quant_conv) output."""
@@ -102,20 +108,23 @@ class Encoder(nn.Module):
         h = self.mid.attn_1._run(h)
         h = self.mid.block_2._run(h)
         gp, cp = ops.gn_conv_pad()
-        ha = gn_act(self.norm_out, h, silu=True, pad=gp)
+        ha = gn_norm(self.norm_out, h, silu=True, pad=gp)
         return ops.conv2d(self._pc_out, ha, pad=cp, out_mode=ops.OUT_NCHW_F32)
 
     @torch.no_grad()
+    def encode_packed(self, x, quant_conv=None):
+        """NCHW image → fp32 NCHW conv_out (∘ ``quant_conv``, the owning first stage's) output."""
+        in_pad = (x.shape[1] + 7) // 8 * 8
+        self.ensure_packed(x.device, in_pad, quant_conv is not None, quant_conv=quant_conv)
+        return self._run(ops.nchw_to_nhwc(x.float(), in_pad))
+
     def forward(self, x):
         if not x.is_cuda:
             raise TypeError("sd_amd.Encoder: HIP path only — move inputs to the GPU")
-        in_pad = (x.shape[1] + 7) // 8 * 8
-        if getattr(self, "_prepared_on", None) != (x.device, in_pad, False):
-            self._prepare(x.device, in_pad)
-        return self._run(ops.nchw_to_nhwc(x.float(), in_pad))
+        return self.encode_packed(x)
 
 
-class Decoder(nn.Module):
+class Decoder(PackedOwner, nn.Module):
     def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions, dropout=0.0,
                  resamp_with_conv=True, in_channels, resolution, z_channels, give_pre_end=False, tanh_out=False,
                  use_linear_attn=False, attn_type="vanilla", **ignorekwargs):
@@ -163,13 +172,11 @@ class Decoder(nn.Module):
         self.conv_out = nn.Conv2d(block_in, out_ch, kernel_size=3, stride=1, padding=1)
         self._block_out = block_in
 
-    def _prepare(self, dev, zc_pad):
+    def _pack(self, dev, zc_pad):
         self._zc_pad = zc_pad
         self._pc_in = ops.PackedConv([(self.conv_in.weight, zc_pad)], self.conv_in.bias, device=dev)
-        for m in self.modules():
-            if m is not self and hasattr(m, "_prepare") and not isinstance(m, Decoder):
-                m._prepare(dev)
-        _gn_prep(self.norm_out, dev)
+        _prepare_blocks(self, dev)
+        prep_norm(self.norm_out, dev)
         self._pc_out = ops.PackedConv([(self.conv_out.weight, self._block_out)], self.conv_out.bias, device=dev)
 
     def _run(self, z_nhwc):
@@ -191,7 +198,7 @@ class Decoder(nn.Module):
         if self.tanh_out:
             raise NotImplementedError("sd_amd: tanh_out is not on the SD path")
         gp, cp = ops.gn_conv_pad()
-        ha = gn_act(self.norm_out, h, silu=True, pad=gp)
+        ha = gn_norm(self.norm_out, h, silu=True, pad=gp)
         return ops.conv2d(self._pc_out, ha, pad=cp, out_mode=ops.OUT_NCHW_F32)
 
     @torch.no_grad()
@@ -199,7 +206,41 @@ class Decoder(nn.Module):
         if not z.is_cuda:
             raise TypeError("sd_amd.Decoder: HIP path only — move inputs to the GPU")
         zc_pad = (z.shape[1] + 7) // 8 * 8
-        if getattr(self, "_prepared_on", None) != (z.device, zc_pad):
-            self._prepare(z.device, zc_pad)
-            self._prepared_on = (z.device, zc_pad)
+        self.ensure_packed(z.device, zc_pad)
         return self._run(ops.nchw_to_nhwc(z.float(), zc_pad))
+
+
+class FirstStage(PackedOwner, nn.Module):
+    """What ``AutoEncoderKL`` and ``VQModel`` share (each sets ``encoder``, ``decoder``, ``quant_conv``,
+    ``post_quant_conv``, ``embed_dim`` and ``z_channels``): the checkpoint loader, and the decode path.  The model
+    owns the pack of its 1x1 ``post_quant_conv`` (a GEMM whose output is zero-padded to 8 channels) and asks its
+    ``Encoder`` / ``Decoder`` to pack themselves with the key it needs."""
+
+    def init_from_ckpt(self, path, ignore_keys=list()):
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        sd = sd.get("state_dict", sd)
+        for k in list(sd.keys()):
+            if any(k.startswith(ik) for ik in ignore_keys):
+                del sd[k]
+        self.load_state_dict(sd, strict=False)
+
+    def prepare(self, device):
+        self.repack(torch.device(device))
+
+    def _pack(self, dev):
+        self._ezp = (self.embed_dim + 7) // 8 * 8
+        self._zcp = (self.z_channels + 7) // 8 * 8
+        w = torch.zeros(self._zcp, self.embed_dim, 1, 1, device=self.post_quant_conv.weight.device)
+        w[: self.z_channels] = self.post_quant_conv.weight.detach()
+        b = torch.zeros(self._zcp, device=w.device)
+        b[: self.z_channels] = self.post_quant_conv.bias.detach()
+        self._pc_pq = ops.PackedConv([(w, self._ezp)], b, device=dev)
+        self.decoder.repack(dev, self._zcp)
+
+    @torch.no_grad()
+    def _decode_packed(self, z, pre_scale: float = 1.0):
+        """post_quant_conv → Decoder on a GPU ``z``; ``pre_scale`` is fused into the layout conversion."""
+        self.ensure_packed(z.device)
+        self.decoder.ensure_packed(z.device, self._zcp)
+        zn = ops.nchw_to_nhwc(z.float(), self._ezp, scale=pre_scale)
+        return self.decoder._run(ops.conv2d(self._pc_pq, zn))

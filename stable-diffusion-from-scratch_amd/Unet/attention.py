@@ -20,7 +20,8 @@ import torch
 from torch import nn
 
 from .. import ops
-from .unet import Normalize, _gn_prep, gn_act
+from ..packing import gn_norm, prep_norm
+from .unet import Normalize
 
 
 class FlashAttentionBlock(nn.Module):
@@ -37,7 +38,7 @@ class FlashAttentionBlock(nn.Module):
         self.proj_out = nn.Conv2d(in_channels, in_channels, kernel_size=1)
 
     def _prepare(self, dev):
-        _gn_prep(self.norm, dev)
+        prep_norm(self.norm, dev)
         w = torch.cat([self.q.weight, self.k.weight, self.v.weight], 0)
         b = torch.cat([self.q.bias, self.k.bias, self.v.bias], 0)
         self._pc_qkv = ops.PackedConv([(w, self.in_channels)], b, device=dev)
@@ -45,7 +46,7 @@ class FlashAttentionBlock(nn.Module):
 
     def _run(self, x):
         B, H, W, C = x.shape
-        xn = gn_act(self.norm, x, silu=False)
+        xn = gn_norm(self.norm, x, silu=False)
         qkv = ops.conv2d(self._pc_qkv, xn).view(B * H * W, 3 * C)
         o = ops.attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], batch=B, heads=self.num_heads, nq=H * W,
                           nk=H * W, head_dim=self.head_dim, scale=self.head_dim ** -0.5)
@@ -71,7 +72,7 @@ class AttentionBlock(nn.Module):
 
     def _run(self, x):
         B, H, W, C = x.shape
-        xn = gn_act(self.norm, x, silu=False)
+        xn = gn_norm(self.norm, x, silu=False)
         qkv = ops.conv2d(self._pc_qkv, xn).view(B * H * W, 3 * C)
         o = ops.attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], batch=B, heads=1, nq=H * W, nk=H * W,
                           head_dim=C, scale=int(C) ** (-0.5))

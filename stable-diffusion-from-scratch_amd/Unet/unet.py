@@ -9,28 +9,17 @@ epilogue of conv2.
 """
 from __future__ import annotations
 
-import torch
 from torch import nn
 
 from .. import ops
+from ..packing import gn_norm, pack_res_tail, pack_upsample_conv, prep_norm, run_res_tail, run_upsample_conv
 
 
 def Normalize(in_channels, num_groups=32):
     return nn.GroupNorm(num_groups=num_groups, num_channels=in_channels, eps=1e-6, affine=True)
 
 
-def _gn_prep(gn, dev):
-    gn._g = gn.weight.detach().to(dev, torch.float32).contiguous()
-    gn._b = gn.bias.detach().to(dev, torch.float32).contiguous()
-
-
-def gn_stats(gn, x):
-    return ops.group_norm_affine(x, gn._g, gn._b, gn.eps, gn.num_groups)
-
-
-def gn_act(gn, x, silu=True, pad=0):
-    """Normalize (+ nonlinearity) of x materialised, zero-bordered by ``pad`` (``sdk_group_norm``)."""
-    return ops.group_norm(x, gn._g, gn._b, gn.eps, gn.num_groups, silu=silu, pad=pad)
+UPSAMPLE_MATERIALISE_MAX_BYTES = 8 << 30   # the VAE Upsample's zero-bordered x2 image (DESIGN §2)
 
 
 class Upsample(nn.Module):
@@ -43,34 +32,13 @@ class Upsample(nn.Module):
         self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1)
 
     def _prepare(self, dev):
-        from ..openai_model.model import UPSAMPLE_FOLD, UPSAMPLE_MATERIALISE
-        self._pc = ops.PackedConv([(self.conv.weight, self.in_channels)], self.conv.bias, device=dev)
-        self._ppc = None
-        if self.in_channels % 64 == 0 and not (UPSAMPLE_FOLD or UPSAMPLE_MATERIALISE):
-            self._ppc = ops.PhaseConv(self.conv.weight, self.in_channels, self.conv.bias, device=dev)
+        self._pc, self._ppc = pack_upsample_conv(self.conv, self.in_channels, dev)
 
     def _run(self, x):
-        # Default: the phase form (openai_model/model.py) — four 2x2 convs over the zero-bordered low-res image;
-        # neither the x2 image nor its temporary exists.  The routes below are the A/B switches and the fallback
-        # for channel counts that are no multiple of 64.
-        from ..openai_model.model import upsample_phase_ok
-        if getattr(self, "_ppc", None) is not None and upsample_phase_ok(x):
-            return ops.conv2d(self._ppc, ops.zero_border(x, 1), phase=True, gn_stats=True)
-        # the output feeds the next ResnetBlock's norm1: the conv emits its GroupNorm statistics.  As in the UNet's
-        # Upsample (openai_model/model.py), the nearest-x2 image is written zero-bordered and the 3x3 conv runs
-        # unmasked with pad 0 on the linear A issue, instead of folding the upsample into every DMA address
-        # (the folded form ran the 512^2 decoder convs at 730-830 TF/s); SD_AMD_UPSAMPLE_FOLD=1 restores it
-        # The materialised image is a temporary of B·(2H+2)·(2W+2)·C·2 bytes beside the input and the output: at C5
-        # (B = 8, 384 -> 768, 256 channels) 2.4 GB; above UPSAMPLE_MATERIALISE_MAX_BYTES the folded form runs instead
-        from ..openai_model.model import UPSAMPLE_FOLD
-        n, h, w, c = x.shape
-        big = n * (2 * h + 2) * (2 * w + 2) * c * 2 > UPSAMPLE_MATERIALISE_MAX_BYTES
-        if UPSAMPLE_FOLD or c % 8 or big:
-            return ops.conv2d(self._pc, x, upsample=True, gn_stats=True)
-        return ops.conv2d(self._pc, ops.upsample_nearest2x_padded(x, 1), pad=0, gn_stats=True)
-
-
-UPSAMPLE_MATERIALISE_MAX_BYTES = 8 << 30   # the VAE Upsample's zero-bordered x2 image (DESIGN §2)
+        # The routes: packing.run_upsample_conv.  The materialised image (the A/B switch, and the fallback for
+        # channel counts that are no multiple of 64) is at C5 (B = 8, 384 -> 768, 256 channels) a 2.4 GB temporary:
+        # above UPSAMPLE_MATERIALISE_MAX_BYTES the folded form runs instead
+        return run_upsample_conv(self._pc, self._ppc, x, materialise_max_bytes=UPSAMPLE_MATERIALISE_MAX_BYTES)
 
 
 class Downsample(nn.Module):
@@ -115,21 +83,11 @@ class ResnetBlock(nn.Module):
                 self.nin_shortcut = nn.Conv2d(in_channels, out_channels, kernel_size=1, stride=1, padding=0)
 
     def _prepare(self, dev):
-        _gn_prep(self.norm1, dev)
-        _gn_prep(self.norm2, dev)
+        prep_norm(self.norm1, dev)
+        prep_norm(self.norm2, dev)
         self._pc1 = ops.PackedConv([(self.conv1.weight, self.in_channels)], self.conv1.bias, device=dev)
-        self._mode = "identity"
-        if self.in_channels != self.out_channels and not self.use_conv_shortcut:
-            self._mode = "fused"
-            self._pc2 = ops.PackedConv([(self.conv2.weight, self.out_channels),
-                                        (self.nin_shortcut.weight, self.in_channels)],
-                                       self.conv2.bias.detach() + self.nin_shortcut.bias.detach(), device=dev)
-        else:
-            self._pc2 = ops.PackedConv([(self.conv2.weight, self.out_channels)], self.conv2.bias, device=dev)
-            if self.in_channels != self.out_channels:
-                self._mode = "conv3"
-                self._pcs = ops.PackedConv([(self.conv_shortcut.weight, self.in_channels)], self.conv_shortcut.bias,
-                                           device=dev)
+        skip = getattr(self, "conv_shortcut" if self.use_conv_shortcut else "nin_shortcut", None)
+        self._tail = pack_res_tail(self.conv2, skip, self.in_channels, self.out_channels, dev)
 
     def _run(self, x, temb=None):
         if temb is not None:
@@ -138,10 +96,5 @@ class ResnetBlock(nn.Module):
         # feed a GroupNorm (norm2 / the next block's norm1, an attention norm or norm_out), so the convs
         # emit its statistics from their epilogues (no statistics pass over the tensor)
         gp, cp = ops.gn_conv_pad()
-        h = ops.conv2d(self._pc1, gn_act(self.norm1, x, silu=True, pad=gp), pad=cp, gn_stats=True)
-        ha = gn_act(self.norm2, h, silu=True, pad=gp)
-        if self._mode == "identity":
-            return ops.conv2d(self._pc2, ha, pad=cp, residual=x, gn_stats=True)
-        if self._mode == "fused":
-            return ops.conv2d(self._pc2, ha, pad=cp, seg2=(x, None, False), gn_stats=True)
-        return ops.conv2d(self._pc2, ha, pad=cp, residual=ops.conv2d(self._pcs, x), gn_stats=True)
+        h = ops.conv2d(self._pc1, gn_norm(self.norm1, x, silu=True, pad=gp), pad=cp, gn_stats=True)
+        return run_res_tail(self._tail, gn_norm(self.norm2, h, silu=True, pad=gp), x, cp)

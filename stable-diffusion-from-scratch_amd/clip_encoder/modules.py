@@ -33,6 +33,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..packing import PackedOwner, f32, prep_norm
 
 VIT_L14_TEXT = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12,
                     num_attention_heads=12, max_position_embeddings=77, layer_norm_eps=1e-5,
@@ -246,19 +247,18 @@ class _EncoderLayer(nn.Module):
         self._pc_fc1 = ops.PackedConv([(self.mlp.fc1.weight, D)], self.mlp.fc1.bias, device=dev)
         self._pc_fc2 = ops.PackedConv([(self.mlp.fc2.weight, self.mlp.fc1.out_features)], self.mlp.fc2.bias,
                                       device=dev)
-        self._ln = [(ln.weight.detach().to(dev, torch.float32).contiguous(),
-                     ln.bias.detach().to(dev, torch.float32).contiguous(), ln.eps)
-                    for ln in (self.layer_norm1, self.layer_norm2)]
+        prep_norm(self.layer_norm1, dev)
+        prep_norm(self.layer_norm2, dev)
 
     def _run(self, x, B, T, heads):
         D = x.shape[1]
-        (g1, b1, e1), (g2, b2, e2) = self._ln
-        qkv = ops.linear(self._pc_qkv, ops.layer_norm(x, g1, b1, e1))
+        n1, n2 = self.layer_norm1, self.layer_norm2
+        qkv = ops.linear(self._pc_qkv, ops.layer_norm(x, n1._g, n1._b, n1.eps))
         d = D // heads
         o = ops.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], batch=B, heads=heads, nq=T, nk=T,
                           head_dim=d, scale=d ** -0.5, causal=True)
         x = ops.linear(self._pc_o, o, residual=x)
-        f = ops.linear(self._pc_fc1, ops.layer_norm(x, g2, b2, e2), act=ops.ACT_QUICK_GELU)
+        f = ops.linear(self._pc_fc1, ops.layer_norm(x, n2._g, n2._b, n2.eps), act=ops.ACT_QUICK_GELU)
         return ops.linear(self._pc_fc2, f, residual=x)
 
 
@@ -268,7 +268,7 @@ class _Encoder(nn.Module):
         self.layers = nn.ModuleList([_EncoderLayer(cfg) for _ in range(cfg["num_hidden_layers"])])
 
 
-class CLIPTextTransformer(nn.Module):
+class CLIPTextTransformer(PackedOwner, nn.Module):
     """transformers' CLIPTextTransformer parameter layout; HIP forward (``_run``)."""
 
     def __init__(self, cfg):
@@ -277,24 +277,19 @@ class CLIPTextTransformer(nn.Module):
         self.embeddings = _Embeddings(cfg)
         self.encoder = _Encoder(cfg)
         self.final_layer_norm = nn.LayerNorm(cfg["hidden_size"], eps=cfg["layer_norm_eps"])
-        self._prepared_on = None
 
-    def _prepare(self, dev):
+    def _pack(self, dev):
         for layer in self.encoder.layers:
             layer._prepare(dev)
-        self._tok = self.embeddings.token_embedding.weight.detach().to(dev, torch.float32).contiguous()
-        self._pos = self.embeddings.position_embedding.weight.detach().to(dev, torch.float32).contiguous()
-        ln = self.final_layer_norm
-        self._lnf = (ln.weight.detach().to(dev, torch.float32).contiguous(),
-                     ln.bias.detach().to(dev, torch.float32).contiguous(), ln.eps)
-        self._prepared_on = dev
+        self._tok = f32(self.embeddings.token_embedding.weight, dev)
+        self._pos = f32(self.embeddings.position_embedding.weight, dev)
+        prep_norm(self.final_layer_norm, dev)
 
     @torch.no_grad()
     def _run(self, ids):
         if not ids.is_cuda:
             raise TypeError("sd_amd.CLIPTextTransformer: HIP path only — move the ids to the GPU")
-        if self._prepared_on != ids.device:
-            self._prepare(ids.device)
+        self.ensure_packed(ids.device)
         ids = ids.to(torch.int64)
         B, T = ids.shape
         if int(ids.min()) < 0 or int(ids.max()) >= self._tok.shape[0]:
@@ -302,8 +297,8 @@ class CLIPTextTransformer(nn.Module):
         x = ops.token_embedding(ids, self._tok, self._pos).view(B * T, -1)
         for layer in self.encoder.layers:
             x = layer._run(x, B, T, self.cfg["num_attention_heads"])
-        g, b, e = self._lnf
-        return ops.layer_norm(x, g, b, e).view(B, T, -1)
+        ln = self.final_layer_norm
+        return ops.layer_norm(x, ln._g, ln._b, ln.eps).view(B, T, -1)
 
 
 class CLIPTextModel(nn.Module):
@@ -317,7 +312,6 @@ class CLIPTextModel(nn.Module):
         # transformers >= 5 saves without the "text_model." prefix; older files and SD checkpoints with it
         sd = {(k if k.startswith("text_model.") else "text_model." + k): v for k, v in state_dict.items()
               if not k.endswith("position_ids")}
-        self.text_model._prepared_on = None
         return super().load_state_dict(sd, strict=strict, assign=assign)
 
 

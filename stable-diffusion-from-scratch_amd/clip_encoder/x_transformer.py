@@ -28,6 +28,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..packing import PackedOwner, f32, prep_norm
 
 DEFAULT_DIM_HEAD = 64
 LN_MAX_DIM = 2048            # sdk_layer_norm: one wave per row, 4 x 64 chunks of 8 channels
@@ -43,10 +44,6 @@ def _refuse_set(where, **options):
     for name, (val, off) in options.items():
         if val != off:
             _refuse(name, where)
-
-
-def _f32(p, dev):
-    return p.detach().to(dev, torch.float32).contiguous()
 
 
 class AbsolutePositionalEmbedding(nn.Module):
@@ -160,15 +157,14 @@ class AttentionLayers(nn.Module):
             self.layers.append(nn.ModuleList([nn.LayerNorm(dim), layer, Residual()]))
 
     def _prepare(self, dev):
-        self._ln = []
         for norm, block, _ in self.layers:
             block._prepare(dev)
-            self._ln.append((_f32(norm.weight, dev), _f32(norm.bias, dev), norm.eps))
+            prep_norm(norm, dev)
 
     def _run(self, x, B, T):
         """x fp16 [B*T, dim] → the same shape after every (LayerNorm → block → + x) pair."""
-        for layer_type, (_, block, _), (g, b, eps) in zip(self.layer_types, self.layers, self._ln):
-            t = ops.layer_norm(x, g, b, eps)
+        for layer_type, (norm, block, _) in zip(self.layer_types, self.layers):
+            t = ops.layer_norm(x, norm._g, norm._b, norm.eps)
             x = block._run(t, x, B, T) if layer_type == "a" else block._run(t, x)
         return x
 
@@ -179,7 +175,7 @@ class Encoder(AttentionLayers):
         super().__init__(causal=False, **kwargs)
 
 
-class TransformerWrapper(nn.Module):
+class TransformerWrapper(PackedOwner, nn.Module):
     def __init__(self, *, num_tokens, max_seq_len, attn_layers, emb_dim=None, max_mem_len=0., emb_dropout=0.,
                  num_memory_tokens=None, tie_embedding=False, use_pos_emb=True):
         super().__init__()
@@ -201,19 +197,12 @@ class TransformerWrapper(nn.Module):
         nn.init.normal_(self.token_emb.weight, std=0.02)
         # part of the checkpoint layout; the embeddings path (return_embeddings=True) never applies it
         self.to_logits = nn.Linear(dim, num_tokens)
-        self._prepared_on = None
-        # packed device copies are rebuilt after any load_state_dict, this module's or a parent's
-        self._register_load_state_dict_pre_hook(self._invalidate)
 
-    def _invalidate(self, *args):
-        self._prepared_on = None
-
-    def _prepare(self, dev):
+    def _pack(self, dev):
         self.attn_layers._prepare(dev)
-        self._tok = _f32(self.token_emb.weight, dev)
-        self._pos = _f32(self.pos_emb.emb.weight, dev)
-        self._lnf = (_f32(self.norm.weight, dev), _f32(self.norm.bias, dev), self.norm.eps)
-        self._prepared_on = dev
+        self._tok = f32(self.token_emb.weight, dev)
+        self._pos = f32(self.pos_emb.emb.weight, dev)
+        prep_norm(self.norm, dev)
 
     @torch.no_grad()
     def forward(self, x, return_embeddings=False, mask=None, return_mems=False, return_attn=False, mems=None,
@@ -232,12 +221,10 @@ class TransformerWrapper(nn.Module):
         B, T = x.shape
         if B < 1 or not 1 <= T <= self.max_seq_len:
             raise ValueError(f"sd_amd.TransformerWrapper: {T} tokens outside [1, max_seq_len = {self.max_seq_len}]")
-        if self._prepared_on != x.device:
-            self._prepare(x.device)
+        self.ensure_packed(x.device)
         ids = x.to(torch.int64)
         if int(ids.min()) < 0 or int(ids.max()) >= self.num_tokens:
             raise ValueError("sd_amd.TransformerWrapper: token id outside the vocabulary")
         h = ops.token_embedding(ids, self._tok, self._pos).view(B * T, -1)
         h = self.attn_layers._run(h, B, T)
-        g, b, e = self._lnf
-        return ops.layer_norm(h, g, b, e).view(B, T, -1)
+        return ops.layer_norm(h, self.norm._g, self.norm._b, self.norm.eps).view(B, T, -1)

@@ -15,8 +15,9 @@ Soundness rules (each one is what a replay reads from memory it does not own):
   was captured with, so model-side cache eviction cannot free memory a replay reads;
 * workspaces (split-K slabs, GroupNorm partials) are never freed while graphs may hold
   their pointers (``ops._Workspace`` retires, never releases, a grown buffer);
-* re-packing the weights (``UNetModel.prepare`` after ``load_state_dict``) bumps the
-  model's ``prepare_generation`` and drops every graph.
+* loading parameters into the model (directly or through any parent module) or re-packing them
+  (``UNetModel.prepare``) moves the model's ``prepare_generation`` (``packing.PackedOwner``) and
+  the next call drops every graph.
 Preconditions: run one eager step first so the conv autotuner, the workspaces and the
 context K/V cache are settled.  The result is a fresh tensor per call, as the eager forward
 returns (a copy of the graph's static output, 1 MiB at the C3 batch: a caller may keep eps

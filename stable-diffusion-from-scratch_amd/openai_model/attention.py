@@ -25,29 +25,12 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..packing import f32, gn_norm, prep_norm
 from .utils import conv_nd, normalization, zero_module
 
 
 def Normalize(in_channels):
     return torch.nn.GroupNorm(num_groups=32, num_channels=in_channels, eps=1e-6, affine=True)
-
-
-def _gn_prep(gn: nn.GroupNorm, dev):
-    gn._g = gn.weight.detach().to(dev, torch.float32).contiguous()
-    gn._b = gn.bias.detach().to(dev, torch.float32).contiguous()
-
-
-def _gn_stats(gn: nn.GroupNorm, x):
-    return ops.group_norm_affine(x, gn._g, gn._b, gn.eps, gn.num_groups)
-
-
-def _gn(gn: nn.GroupNorm, x, silu=False):
-    return ops.group_norm(x, gn._g, gn._b, gn.eps, gn.num_groups, silu=silu)
-
-
-def _ln_prep(ln: nn.LayerNorm, dev):
-    ln._g = ln.weight.detach().to(dev, torch.float32).contiguous()
-    ln._b = ln.bias.detach().to(dev, torch.float32).contiguous()
 
 
 # fused to_q + attention + to_out kernel for cross-attention on the cached context (xattn.hip),
@@ -171,7 +154,7 @@ class CrossAttention(nn.Module):
         self._ptl_o = (ops.PackedTokenLinear(self.to_out[0].weight, self.to_out[0].bias, dev)
                        if self.self_attn and ops.token_linear_supported(inner, self.to_out[0].out_features) else None)
         if not self.self_attn:
-            self._bo32 = self.to_out[0].bias.detach().to(dev, torch.float32).contiguous()
+            self._bo32 = f32(self.to_out[0].bias, dev)
             self._pc_reassoc = None    # per-head GEMM weights of the reassociated per-prompt matrices (lazy)
 
     def context_kv(self, ctx2d, L=None):
@@ -302,7 +285,7 @@ class BasicTransformerBlock(nn.Module):
         for m in (self.attn1, self.attn2, self.ff):
             m._prepare(dev)
         for n in (self.norm1, self.norm2, self.norm3):
-            _ln_prep(n, dev)
+            prep_norm(n, dev)
 
     def _run(self, tok, B, N, kv=None, Lc=None, t=None):
         """``t``: norm1(tok) when the producer of ``tok`` emitted it (token_linear with a norm)."""
@@ -342,7 +325,7 @@ class SpatialTransformer(nn.Module):
         self.proj_out = zero_module(nn.Conv2d(inner_dim, in_channels, kernel_size=1, stride=1, padding=0))
 
     def _prepare(self, dev):
-        _gn_prep(self.norm, dev)
+        prep_norm(self.norm, dev)
         self._pc_in = ops.PackedConv([(self.proj_in.weight, self.in_channels)], self.proj_in.bias, device=dev)
         self._ptl_in = (ops.PackedTokenLinear(self.proj_in.weight, self.proj_in.bias, dev)
                         if ops.token_linear_supported(self.in_channels, self.inner_dim) else None)
@@ -357,7 +340,7 @@ class SpatialTransformer(nn.Module):
         B, H, W, Cc = x.shape
         # GN materialised by one streaming pass, then the LDS-DMA GEMM (a GN prologue forces the
         # register-staged kernel: 150-190 TF/s on these shapes vs 330-650 for apply + DMA GEMM)
-        xn = _gn(self.norm, x)
+        xn = gn_norm(self.norm, x, silu=False)
         t1 = None
         if TOKEN_LINEAR and self._ptl_in is not None and xn.is_contiguous():
             # proj_in + the first block's norm1 in one launch (the LayerNorm rows from the same tile)

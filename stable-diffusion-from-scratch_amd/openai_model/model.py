@@ -29,6 +29,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..packing import PackedOwner, f32, pack_res_tail, pack_upsample_conv, run_res_tail, run_upsample_conv
 from .attention import AttentionBlock, SpatialTransformer
 from .utils import avg_pool_nd, conv_nd, linear, normalization, timestep_frequencies, zero_module
 
@@ -84,24 +85,9 @@ class Downsample(nn.Module):
         return ops.conv2d(self._pc, x, stride=2, pad=self.padding, gn_stats=True)
 
 
-# The Upsample modules (this one and the VAE decoder's) run nearest-x2 + conv3x3 in the phase form: four 2x2 convs
-# over the zero-bordered low-res image, one per output parity (ops.PhaseConv, 4/9 of the FLOPs, no x2 image).
-# SD_AMD_UPSAMPLE_MATERIALISE=1 restores the previous route for A/B runs (the nearest-x2 image written
-# zero-bordered, a 3x3 conv over it with pad 0); SD_AMD_UPSAMPLE_FOLD=1 the upsample folded into the 3x3 conv's
-# DMA addresses.
-UPSAMPLE_FOLD = __import__("os").environ.get("SD_AMD_UPSAMPLE_FOLD", "0") == "1"
-UPSAMPLE_MATERIALISE = __import__("os").environ.get("SD_AMD_UPSAMPLE_MATERIALISE", "0") == "1"
-
-
-def upsample_phase_ok(x, padding=1):
-    """The phase form needs one NHWC source with whole 64-channel K blocks (and the conv's padding 1)."""
-    return not (UPSAMPLE_FOLD or UPSAMPLE_MATERIALISE) and not isinstance(x, tuple) and x.shape[-1] % 64 == 0 \
-        and padding == 1
-
-
 class Upsample(nn.Module):
     """Reference ``model.py:100-131``: nearest x2 + conv3x3 (the phase form; else the upsample materialised
-    zero-bordered, or folded into the conv's loads)."""
+    zero-bordered, or folded into the conv's loads: ``packing.run_upsample_conv``)."""
 
     def __init__(self, channels, use_conv, dims=2, out_channels=None, padding=1):
         super().__init__()
@@ -117,19 +103,12 @@ class Upsample(nn.Module):
 
     def _prepare(self, dev):
         if self.use_conv:
-            self._pc = ops.PackedConv([(self.conv.weight, self.channels)], self.conv.bias, device=dev)
-            self._ppc = None
-            if self.channels % 64 == 0 and self.padding == 1 and not (UPSAMPLE_FOLD or UPSAMPLE_MATERIALISE):
-                self._ppc = ops.PhaseConv(self.conv.weight, self.channels, self.conv.bias, device=dev)
+            self._pc, self._ppc = pack_upsample_conv(self.conv, self.channels, dev, self.padding)
 
     def _run(self, x):
         if not self.use_conv:
             return ops.group_norm_resample(x, None, "up")[1]
-        if getattr(self, "_ppc", None) is not None and upsample_phase_ok(x, self.padding):
-            return ops.conv2d(self._ppc, ops.zero_border(x, 1), phase=True, gn_stats=True)
-        if UPSAMPLE_FOLD or isinstance(x, tuple) or x.shape[-1] % 8:
-            return ops.conv2d(self._pc, x, upsample=True, pad=self.padding, gn_stats=True)
-        return ops.conv2d(self._pc, ops.upsample_nearest2x_padded(x, self.padding), pad=0, gn_stats=True)
+        return run_upsample_conv(self._pc, self._ppc, x, self.padding)
 
 
 class ResBlock(TimestepBlock):
@@ -177,19 +156,9 @@ class ResBlock(TimestepBlock):
     def _prepare(self, dev):
         self.in_layers[0]._prepare(dev)
         self.out_layers[0]._prepare(dev)
-        c1, c2 = self.in_layers[2], self.out_layers[3]
+        c1 = self.in_layers[2]
         self._pc1 = ops.PackedConv([(c1.weight, self.channels)], c1.bias, device=dev)
-        sk = self.skip_connection
-        self._skip_mode = "identity"
-        if isinstance(sk, nn.Conv2d) and sk.kernel_size[0] == 1:
-            self._skip_mode = "fused"
-            self._pc2 = ops.PackedConv([(c2.weight, self.out_channels), (sk.weight, self.channels)],
-                                       c2.bias.detach() + sk.bias.detach(), device=dev)
-        else:
-            self._pc2 = ops.PackedConv([(c2.weight, self.out_channels)], c2.bias, device=dev)
-            if isinstance(sk, nn.Conv2d):
-                self._skip_mode = "conv3"
-                self._pc_skip = ops.PackedConv([(sk.weight, self.channels)], sk.bias, device=dev)
+        self._tail = pack_res_tail(self.out_layers[3], self.skip_connection, self.channels, self.out_channels, dev)
 
     def _run(self, x, emb_all, emb_off):
         B, H, W, _ = ops.src_shape(x)
@@ -208,15 +177,10 @@ class ResBlock(TimestepBlock):
         else:
             h = ops.conv2d(self._pc1, xa, pad=cp, row_bias=(emb_all, emb_off), gn_stats=True)
             ha = self.out_layers[0].norm(h, silu=True, pad=gp)
-        if self._skip_mode == "identity":
-            return ops.conv2d(self._pc2, ha, pad=cp, residual=x, gn_stats=True)
-        if self._skip_mode == "fused":
-            return ops.conv2d(self._pc2, ha, pad=cp, seg2=(x, None, False), gn_stats=True)
-        skip = ops.conv2d(self._pc_skip, x)
-        return ops.conv2d(self._pc2, ha, pad=cp, residual=skip, gn_stats=True)
+        return run_res_tail(self._tail, ha, x, cp)
 
 
-class UNetModel(nn.Module):
+class UNetModel(PackedOwner, nn.Module):
     """Reference ``model.py:259-595``.  See the module docstring for the execution plan."""
 
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks,
@@ -327,20 +291,18 @@ class UNetModel(nn.Module):
                 self.output_blocks.append(TimestepEmbedSequential(*layers))
         self.out = nn.Sequential(normalization(ch), nn.SiLU(),
                                  zero_module(conv_nd(dims, model_channels, out_channels, 3, padding=1)))
-        self._prepared_on = None
         self._ctx_cache = None
 
-    # ------------------------------------------------------------------ packing
-    def load_state_dict(self, *args, **kwargs):
-        self._prepared_on = None
-        self._ctx_cache = None
-        return super().load_state_dict(*args, **kwargs)
-
-    @torch.no_grad()
+    # ------------------------------------------------------------------ packing (lifecycle: packing.PackedOwner)
     def prepare(self, device):
         """Pack weights (NHWC fp16, fused segments) on ``device``.  Called lazily by forward;
         call again after modifying parameters in place."""
-        dev = torch.device(device)
+        self.repack(torch.device(device))
+
+    def _packs_dropped(self):
+        self._ctx_cache = None          # K/V (and reassociated weights) projected with the old packs
+
+    def _pack(self, dev):
         resblocks = [m for m in self.modules() if isinstance(m, ResBlock)]
         off = 0
         ws, bs = [], []
@@ -367,12 +329,8 @@ class UNetModel(nn.Module):
         self._freqs = timestep_frequencies(self.model_channels).to(dev)
         self._label_table = None
         if self.num_classes is not None:
-            self._label_table = self.label_emb.weight.detach().to(dev, torch.float32).contiguous()
+            self._label_table = f32(self.label_emb.weight, dev)
         self._sts = [m for m in self.modules() if isinstance(m, SpatialTransformer)]
-        self._prepared_on = dev
-        self._ctx_cache = None
-        # packed weights were replaced: graphs captured on the old ones must be dropped
-        self.prepare_generation = getattr(self, "prepare_generation", 0) + 1
 
     # contexts whose K/V stay resident (cond, uncond, their CFG concat, one spare)
     CONTEXT_CACHE_SIZE = 4
@@ -454,8 +412,7 @@ class UNetModel(nn.Module):
                                  f"{self.in_channels}")
         if not x.is_cuda:
             raise TypeError("sd_amd.UNetModel: HIP path only — move inputs to the GPU")
-        if self._prepared_on != x.device:
-            self.prepare(x.device)
+        self.ensure_packed(x.device)
         t = timesteps
         if not torch.is_tensor(t):
             t = torch.tensor(t)

@@ -11,27 +11,22 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..packing import gn_affine, gn_norm, prep_norm
 
 
 class GroupNorm32(nn.GroupNorm):
     """Reference ``openai_model/utils.py:15-22`` (32 groups, eps 1e-5).  ``stats`` returns
     the per-(batch, channel) affine the conv kernel applies in its prologue."""
 
-    def _prepare(self, dev):
-        self._g = self.weight.detach().to(dev, torch.float32).contiguous()
-        self._b = self.bias.detach().to(dev, torch.float32).contiguous()
-
-    def stats(self, x):
-        return ops.group_norm_affine(x, self._g, self._b, self.eps, self.num_groups)
+    _prepare = prep_norm
+    stats = gn_affine
 
     def scale_shift(self, x):
         """(scale, shift) [B, C] of this GroupNorm of x (from the producers' statistics) for a conv that
         applies it to its own staged input (ops.group_norm_scale_shift)."""
         return ops.group_norm_scale_shift(x, self._g, self._b, self.eps, self.num_groups)
 
-    def norm(self, x, silu=True, pad=0):
-        """GroupNorm (+ SiLU) of x materialised (zero-bordered by ``pad``) — one ``sdk_group_norm``."""
-        return ops.group_norm(x, self._g, self._b, self.eps, self.num_groups, silu=silu, pad=pad)
+    norm = gn_norm
 
     def norm_film(self, x, film, film_off, silu=True, pad=0):
         """``norm`` with FiLM conditioning, ``GN(x) * (1 + f) + g`` with (f, g) = ``film[:, off : off + 2C]`` — one

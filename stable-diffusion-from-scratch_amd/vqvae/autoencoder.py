@@ -18,12 +18,11 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from .. import ops
-from ..Encoder_Decoder.encoder import Decoder, Encoder
+from ..Encoder_Decoder.encoder import Decoder, Encoder, FirstStage
 from .quantize import VectorQuantize2 as VectorQuantizer
 
 
-class VQModel(nn.Module):
+class VQModel(FirstStage):
     def __init__(self, ddconfig, n_embed, embed_dim, lossconfig=None, ckpt_path=None, ignore_keys=[],
                  image_key="image", colorize_nlabels=None, monitor=None, batch_resize_range=None,
                  scheduler_config=None, lr_g_factor=1.0, remap=None, sane_index_shape=False, use_ema=False):
@@ -49,56 +48,21 @@ class VQModel(nn.Module):
         self.use_ema = use_ema
         self.scheduler_config = scheduler_config
         self.lr_g_factor = lr_g_factor
-        self._prepared_on = None
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
-
-    def init_from_ckpt(self, path, ignore_keys=list()):
-        sd = torch.load(path, map_location="cpu", weights_only=True)
-        sd = sd.get("state_dict", sd)
-        for k in list(sd.keys()):
-            if any(k.startswith(ik) for ik in ignore_keys):
-                del sd[k]
-        self.load_state_dict(sd, strict=False)
-
-    def load_state_dict(self, *args, **kwargs):
-        self._prepared_on = None
-        self.encoder._prepared_on = None
-        self.quantize._norms = None
-        return super().load_state_dict(*args, **kwargs)
-
-    @torch.no_grad()
-    def prepare(self, device):
-        dev = torch.device(device)
-        self._ezp = (self.embed_dim + 7) // 8 * 8
-        self._zcp = (self.z_channels + 7) // 8 * 8
-        w = torch.zeros(self._zcp, self.embed_dim, 1, 1, device=self.post_quant_conv.weight.device)
-        w[: self.z_channels] = self.post_quant_conv.weight.detach()
-        b = torch.zeros(self._zcp, device=w.device)
-        b[: self.z_channels] = self.post_quant_conv.bias.detach()
-        self._pc_pq = ops.PackedConv([(w, self._ezp)], b, device=dev)
-        self.decoder._prepare(dev, self._zcp)
-        self.decoder._prepared_on = (dev, self._zcp)
-        self._prepared_on = dev
 
     @torch.no_grad()
     def _encode_h(self, x):
         """Encoder ∘ quant_conv: NCHW image → fp32 NCHW [B, embed_dim, h, w]."""
         if not torch.is_tensor(x) or not x.is_cuda:
             raise TypeError("sd_amd.VQModel: HIP path only — move inputs to the GPU")
-        in_pad = (x.shape[1] + 7) // 8 * 8
-        if getattr(self.encoder, "_prepared_on", None) != (x.device, in_pad, True):
-            self.encoder._prepare(x.device, in_pad, quant_conv=self.quant_conv)
-        return self.encoder._run(ops.nchw_to_nhwc(x.float(), in_pad))
+        return self.encoder.encode_packed(x, quant_conv=self.quant_conv)
 
     @torch.no_grad()
     def _decode_quant(self, quant, pre_scale: float = 1.0):
         if not torch.is_tensor(quant) or not quant.is_cuda:
             raise TypeError("sd_amd.VQModel: HIP path only — move inputs to the GPU")
-        if self._prepared_on != quant.device:
-            self.prepare(quant.device)
-        zn = ops.nchw_to_nhwc(quant.float(), self._ezp, scale=pre_scale)
-        return self.decoder._run(ops.conv2d(self._pc_pq, zn))
+        return self._decode_packed(quant, pre_scale)
 
     @torch.no_grad()
     def encode(self, x):

@@ -25,9 +25,10 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..packing import PackedOwner
 
 
-class VectorQuantize2(nn.Module):
+class VectorQuantize2(PackedOwner, nn.Module):
     def __init__(self, n_e, e_dim, beta, remap=None, unknown_index="random", sane_index_shape=False, legacy=True):
         super().__init__()
         self.n_e = n_e
@@ -46,15 +47,9 @@ class VectorQuantize2(nn.Module):
         else:
             self.re_embed = n_e
         self.sane_index_shape = sane_index_shape
-        self._norms = None
 
-    def load_state_dict(self, *args, **kwargs):
-        self._norms = None
-        return super().load_state_dict(*args, **kwargs)
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        self._norms = None                              # also when a parent module loads
-        return super()._load_from_state_dict(*args, **kwargs)
+    def _pack(self, *weight_key):
+        self._norms = ops.vq_code_norms(self.embedding.weight.detach())
 
     def _codebook(self, device):
         """(fp32 contiguous codebook on ``device``, cached ‖e‖²)."""
@@ -62,10 +57,8 @@ class VectorQuantize2(nn.Module):
         if w.device != device or w.dtype != torch.float32 or not w.is_contiguous():
             raise TypeError("sd_amd.VectorQuantize2: the codebook must be fp32 on the input's device "
                             "(move the module to the GPU)")
-        key = (w.data_ptr(), w._version, w.device)
-        if self._norms is None or self._norms[0] != key:
-            self._norms = (key, ops.vq_code_norms(w))
-        return w, self._norms[1]
+        self.ensure_packed(w.device, w.data_ptr(), w._version)
+        return w, self._norms
 
     @torch.no_grad()
     def nearest(self, z):

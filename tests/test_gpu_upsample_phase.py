@@ -227,6 +227,7 @@ def test_upsample_modules_both_routes_vs_oracle(ops, sdk, which, monkeypatch):
     (the A/B switch), each against the oracle's interpolate + conv, at the conv parity limit of
     tests/test_gpu_kernels.py (rel-L2 2e-3)."""
     from oracle import unet_ref, vae_ref
+    from sd_amd import packing as P
     from sd_amd.openai_model import model as M
     from sd_amd.Unet import unet as V
     torch.manual_seed(3)
@@ -249,7 +250,7 @@ def test_upsample_modules_both_routes_vs_oracle(ops, sdk, which, monkeypatch):
 
     monkeypatch.setattr(ops, "conv2d", spy)
     for materialise in (False, True):
-        monkeypatch.setattr(M, "UPSAMPLE_MATERIALISE", materialise)
+        monkeypatch.setattr(P, "UPSAMPLE_MATERIALISE", materialise)
         y = mod._run(x.to(DEV))
         assert seen[-1] == (not materialise), "the switch selects the route"
         assert y.shape == ref.shape
