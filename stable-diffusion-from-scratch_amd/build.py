@@ -20,6 +20,7 @@ def _units():
     """(source, object stem, extra defines) per compiled object."""
     yield "conv_plan.hip", "conv_plan", []
     yield "conv_small.hip", "conv_small", []
+    yield "conv_rowpanel.hip", "conv_rowpanel", []
     for k in range(1, CONV_TILE_PARTS + 1):
         yield "conv_tile.hip", f"conv_tile_p{k}", [f"-DSDK_CONV_PART={k}"]
     for src in SOURCES:
@@ -46,8 +47,9 @@ EXTRA = {"attention.hip": ["-mno-amdgpu-ieee", "-fno-honor-nans"],
 # it is reported as a warning (it costs time: scratch round trips in the K loop)
 REMARK = "-Rpass-analysis=kernel-resource-usage"
 # the wide attention kernel (attention_wide.hip) sits at 168 VGPRs with one workgroup per CU: a spill would put
-# scratch round trips into every 32-key tile, so it must build without scratch too
-NO_SCRATCH = re.compile(r"token_linear320_kernel|attn_wide_kernel")
+# scratch round trips into every 32-key tile, so it must build without scratch too; the row-panel conv kernel
+# (conv_rowpanel.hip) holds 160 long-lived registers per lane at two waves per SIMD: a spill there lands in its MFMA loop
+NO_SCRATCH = re.compile(r"token_linear320_kernel|attn_wide_kernel|conv_rowpanel_kernel")
 WARN_SCRATCH = re.compile(r"conv_glds_kernel|conv_ph_kernel|ff_geglu_kernel|xattn_block_kernel|attn_fwd_kernel|vq_nearest_")
 _RES = re.compile(r"remark: (?:Function Name: (\S+)|\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+))")
 

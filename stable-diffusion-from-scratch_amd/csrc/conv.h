@@ -105,18 +105,22 @@ constexpr int SK_MAXM = 64, SK_PF = 8;
 // The sublist a row sits in is the conv_tile.hip part that instantiates its kernel (P0: none).  Families: NONE no such id;
 // IGEMM register-staged conv_igemm_kernel; GLDS the LDS-DMA tile conv_glds_kernel; PH32 / PH16 the phased 256x256
 // conv_ph_kernel on 32x32x16 / 16x16x32; DIRECT (<= 8 output channels); SKINNY (<= 64 rows); DIAG a phased
-// ablation (wrong outputs by design, launched by the diagnostics build only); RETIRED named, never planned.
-enum class Fam { NONE, IGEMM, GLDS, PH32, PH16, DIRECT, SKINNY, DIAG, RETIRED };
+// ablation (wrong outputs by design, launched by the diagnostics build only); RETIRED named, never planned;
+// ROWPANEL the row-panel-stationary conv_rowpanel_kernel (conv_rowpanel.hip: 1x1, cin <= 320; TBM x TBN is the
+// 256-row panel and the 160-column W chunk of its N loop), reached only when forced or tuned, never scored.
+enum class Fam { NONE, IGEMM, GLDS, PH32, PH16, DIRECT, SKINNY, DIAG, RETIRED, ROWPANEL };
 
 // variant 5 (256x320 on 32x32x16, 16 waves) spilled at the 128-VGPR cap of 4 waves per SIMD; its row keeps the
 // name and carries the config of 22, the same tile on 16x16x32 (8 to 16 B/lane of scratch: not spill-free either), which
 // a forced 5 runs as after a one-time warning.  36 / 37 (halo tiles) and 39 (the 8-wave 256x320 on 32x32x16, spilled,
-// never built) have no row: unknown.
+// never built) have no row: unknown.  41 .. 48 have none either: tests/golden/conv_plans.npz records them as unknown
+// (names up to 48, forced ids up to 43), so the first id a new kernel can take is 49.
 #define SDK_CONV_VARIANTS_P0(X, P)                                                                      \
   X(P, 0, IGEMM, CfgIgemm, 0, 2, true, "conv_igemm_kernel")                                             \
   X(P, 5, RETIRED, Cfg256x320m, 0, 1, false, "conv_glds_kernel<Cfg<256,320,8,2>>")                      \
   X(P, 34, DIRECT, CfgUntiled, 0, 1, false, "conv_direct_kernel")                                       \
-  X(P, 35, SKINNY, CfgUntiled, 0, 1, false, "conv_skinny_kernel")
+  X(P, 35, SKINNY, CfgUntiled, 0, 1, false, "conv_skinny_kernel")                                       \
+  X(P, 49, ROWPANEL, CfgRowPanel, 0, 1, false, "conv_rowpanel_kernel")
 #define SDK_CONV_VARIANTS_P1(X, P)                                                                      \
   X(P, 2, GLDS, Cfg256x256, 0, 1, true, "conv_glds_kernel<Cfg<256,256,2,4>>")                           \
   X(P, 3, GLDS, Cfg256x128, 0, 1, true, "conv_glds_kernel<Cfg<256,128,4,2>>")                           \
@@ -162,7 +166,7 @@ enum class Fam { NONE, IGEMM, GLDS, PH32, PH16, DIRECT, SKINNY, DIAG, RETIRED };
 #define SDK_CONV_VARIANTS(X)                                                                            \
   SDK_CONV_VARIANTS_P0(X, 0) SDK_CONV_VARIANTS_P1(X, 1) SDK_CONV_VARIANTS_P2(X, 2) SDK_CONV_VARIANTS_P3(X, 3) \
   SDK_CONV_VARIANTS_P4(X, 4) SDK_CONV_VARIANTS_P5(X, 5)
-constexpr int kVariantIds = 41;      // ids are 0 .. 40 (a row past the end does not compile)
+constexpr int kVariantIds = 50;      // ids are 0 .. 49 (a row past the end does not compile)
 constexpr int kRetiredRunsAs = 22;
 
 #ifdef SDK_CONV_DIAGNOSTICS
@@ -178,6 +182,8 @@ SDK_HIDDEN int launch_splitk_reduce(const Params& p, hipStream_t s);
 SDK_HIDDEN int launch_splitk_reduce_gn(const Params& p, hipStream_t s);
 SDK_HIDDEN int launch_direct(const Params& p, hipStream_t s);
 SDK_HIDDEN int launch_skinny(const Params& p, hipStream_t s);
+// conv_rowpanel.hip: the row-panel-stationary kernel
+SDK_HIDDEN int launch_rowpanel(const Params& p, hipStream_t s);
 // conv_tile.hip, one object per part k (-DSDK_CONV_PART=k): the tile kernels of the rows of SDK_CONV_VARIANTS_Pk
 #define SDK_PART_DECL(k) SDK_HIDDEN int launch_part##k(int v, const Params& p, hipStream_t s)
 SDK_PART_DECL(1); SDK_PART_DECL(2); SDK_PART_DECL(3); SDK_PART_DECL(4); SDK_PART_DECL(5);

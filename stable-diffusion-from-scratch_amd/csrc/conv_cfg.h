@@ -77,6 +77,11 @@ struct PhCfg {
 using PhCfg8 = PhCfg<8, 6>;
 using PhCfg10 = PhCfg<10, 8>;
 
+// the row-panel-stationary kernel (conv_rowpanel.hip): a workgroup keeps a TBM-row panel of A in registers and walks
+// N in TBN-column chunks of W; MAXK bounds the panel's register cost (MAXK / 4 VGPRs per lane), MAXN the bias
+// vector staged in LDS for the whole launch
+struct CfgRowPanel { static constexpr int TBM = 256, TBN = 160, MAXK = 320, MAXN = 2560; };
+
 // the tile of a variant-table row's config type
 struct CfgIgemm { static constexpr int TBM = BM, TBN = BN; };
 struct CfgUntiled { static constexpr int TBM = 0, TBN = 0; };   // direct / skinny: no BM x BN tiling

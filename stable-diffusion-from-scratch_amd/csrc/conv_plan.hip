@@ -262,10 +262,21 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
     forced = kRetiredRunsAs;
     fr = &kVariants.row[forced];
   }
+  // the row-panel kernel (conv_rowpanel.hip): a 1x1 over one source with K = cin <= 320 in whole 32-wide K-steps,
+  // fp16 NHWC rows, bias and residual only (no embedding row), one W for every image, no split of K
+  bool rowpanel_ok = false;
+  {
+    const sdk_conv_src& g = a->seg[0];
+    rowpanel_ok = !transform && !phase && a->nseg == 1 && g.ksize == 1 && g.stride == 1 && g.pad == 0 &&
+                  g.pad_end == 0 && !g.upsample && (!g.src1 || g.c_split >= g.cin) && g.cin % 32 == 0 &&
+                  g.cin <= CfgRowPanel::MAXK && a->cout <= CfgRowPanel::MAXN && a->out_mode == SDK_OUT_NHWC_F16 &&
+                  !a->row_bias && !p.wbs && a->split_k <= 1 && !a->split_inlaunch;
+  }
   // honoured when the kernel can run this conv: the register-staged kernel takes every operand but per-image
   // weights, the others need a transform-free one, a GEGLU-pairing epilogue for the GEGLU output, the LDS-DMA
   // tile family for the phase form, and per-image weights need M-tiles inside one image
-  if (fr && (fr->fam == Fam::IGEMM || !transform) && (fr->geglu || a->out_mode != SDK_OUT_GEGLU_F16) &&
+  if (fr && (fr->fam != Fam::ROWPANEL || rowpanel_ok) &&
+      (fr->fam == Fam::IGEMM || !transform) && (fr->geglu || a->out_mode != SDK_OUT_GEGLU_F16) &&
       (phase ? lds_dma_tile(*fr) : (!p.wbs || (fr->fam != Fam::IGEMM && p.hw_out % fr->bm == 0)))) {
     var = forced;
     best_split = 0;
@@ -293,7 +304,7 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
       while (tiles * split < 256 * row.per_cu && kt / (split * 2) >= 8 && split < 16) split *= 2;
     }
   }
-  if (a->out_mode == SDK_OUT_GEGLU_F16 || a->cout % 8) split = 1;
+  if (a->out_mode == SDK_OUT_GEGLU_F16 || a->cout % 8 || row.fam == Fam::ROWPANEL) split = 1;
   if (split > kt) split = kt;
   p.kt_per_split = (kt + split - 1) / split;
   split = (kt + p.kt_per_split - 1) / p.kt_per_split;
@@ -377,6 +388,7 @@ extern "C" int sdk_conv2d(const sdk_conv_args* a, sdk_stream_t stream) {
     case Fam::IGEMM: rc = launch_igemm(p, s); break;
     case Fam::DIRECT: rc = launch_direct(p, s); break;
     case Fam::SKINNY: rc = launch_skinny(p, s); break;
+    case Fam::ROWPANEL: rc = launch_rowpanel(p, s); break;
     default:   // the tile kernels, each in its compile part (part 0 rows have no launcher: never planned)
       rc = row.part ? kPartLaunch[row.part](p.variant, p, s)
                     : fail(SDK_EINVAL, "conv2d: planned variant " + std::to_string(p.variant) + " has no kernel");
