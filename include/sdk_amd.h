@@ -527,6 +527,41 @@ typedef struct {
 
 int sdk_posterior_step_ex(const sdk_posterior_ex_args* a, sdk_stream_t stream);
 
+/* Multistep sampler update (extension: PLMS as CompVis' ldm/models/diffusion/plms.py, DPM-Solver++(2M)
+ * on the DDIM timestep grid), one launch, fp32, every product, sum and quotient rounded on its own.  e below is
+ * the model output after the guidance combine and v conversion of sdk_ddim_step (step.e, e_uncond, guidance,
+ * v_param, v_sqrt_a, v_sqrt_1ma); step.noise must be NULL and step.sigma 0, temperature is ignored.
+ *   SDK_MULTISTEP_PLMS         hist[0..nhist-1] hold the guided e of the previous 1-3 steps, most recent first:
+ *                                nhist 0  e' = e                          1  e' = (3 e - h1) / 2
+ *                                      2  e' = ((23 e - 16 h1) + 5 h2) / 12
+ *                                      3  e' = (((55 e - 59 h1) + 37 h2) - 9 h3) / 24        (true divisions)
+ *                              then pred_x0 and x_prev are what sdk_ddim_step computes at sigma 0 with e' for e
+ *                              (v conversion, if any, happens before: e' is never converted); hist_out = e.
+ *   SDK_MULTISTEP_PLMS_WARMUP  the first step's second half: e' = (e + e_next) / 2, e_next the (guided, eps)
+ *                              output of the model at the tentative x_prev; the rest as above.
+ *   SDK_MULTISTEP_DPM          D = (x - sqrt_one_minus_at e) / sqrt_at (the bits of sdk_ddim_step's pred_x0);
+ *                              nhist 0: x_prev = c_x x + c_0 D;  nhist 1: x_prev = (c_x x + c_0 D) + c_1 hist[0],
+ *                              hist[0] the previous step's D; pred_x0 = D, hist_out = D.  c_x, c_0, c_1 are the
+ *                              caller's fp32 coefficients; dir_coef and sqrt_a_prev are ignored.
+ * pred_x0 and hist_out are written when non-NULL.  hist_out may alias any history pointer (the ring's oldest
+ * entry) and blend.out may alias step.x: each element is read before the same thread writes it.  blend as in
+ * sdk_ddim_ex_args.  Any n >= 1; 16-byte accesses when every pointer is 16-byte aligned, scalar otherwise and for
+ * the tail. */
+enum { SDK_MULTISTEP_PLMS = 0, SDK_MULTISTEP_PLMS_WARMUP = 1, SDK_MULTISTEP_DPM = 2 };
+
+typedef struct {
+  sdk_ddim_args step;
+  const float* hist[3];
+  const float* e_next;
+  float* hist_out;
+  int32_t form, nhist;
+  float c_x, c_0, c_1;
+  int32_t reserved;        /* 0 */
+  sdk_masked_q_args blend;
+} sdk_multistep_args;
+
+int sdk_multistep_step(const sdk_multistep_args* a, sdk_stream_t stream);
+
 /* sdk_nchw_to_nhwc (scale 1) of torch.cat(src, 1) without the concatenated fp32 tensor
  * (DiffusionWrapper.forward 'concat' / 'hybrid', Diffusion/ddpm.py:51-63): nsrc (1..4) NCHW fp32 sources
  * [batch][channels[i]][hw] -> y NHWC fp16 [batch][hw][c_pad]; source i lands at channel offset

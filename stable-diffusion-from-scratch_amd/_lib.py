@@ -108,6 +108,11 @@ class DdimExArgs(C.Structure):
     _fields_ = [("step", DdimArgs), ("pred_x0_in", i32), ("drop_scale", f32), ("keep", vp), ("blend", MaskedQArgs)]
 
 
+class MultistepArgs(C.Structure):
+    _fields_ = [("step", DdimArgs), ("hist", vp * 3), ("e_next", vp), ("hist_out", vp), ("form", i32), ("nhist", i32),
+                ("c_x", f32), ("c_0", f32), ("c_1", f32), ("reserved", i32), ("blend", MaskedQArgs)]
+
+
 class PosteriorExArgs(C.Structure):
     _fields_ = [("step", PosteriorArgs), ("keep", vp), ("drop_scale", f32)]
 
@@ -132,13 +137,14 @@ OUT_NHWC_F16, OUT_NCHW_F32, OUT_GEGLU_F16, OUT_ROWS_F32 = 0, 1, 2, 3
 RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_BICUBIC, RESIZE_AREA = range(4)
 ACT_NONE, ACT_QUICK_GELU = 0, 1
 ATTN_AUTO, ATTN_NW4, ATTN_NW8, ATTN_NW8_STAG, ATTN_QB2, ATTN_WIDE = range(6)
+MULTISTEP_PLMS, MULTISTEP_PLMS_WARMUP, MULTISTEP_DPM = range(3)      # SDK_MULTISTEP_*
 ATTN_WIDE_ROWS, ATTN_WIDE_KT = 64, 32      # SDK_ATTN_WIDE_ROWS / SDK_ATTN_WIDE_KT
 RESAMPLE_AVGPOOL2, RESAMPLE_NEAREST2 = 0, 1
 GN_STATS = ("given", "slice", "chunked", "parts")              # SDK_GN_STATS_*
 GN_APPLY = ("none", "in_stats", "flat", "row", "stride")       # SDK_GN_APPLY_*
 
 EXPORTS = ["sdk_conv2d_plan", "sdk_conv2d", "sdk_group_norm_workspace", "sdk_group_norm_affine", "sdk_group_norm_apply", "sdk_group_norm_apply_padded", "sdk_group_norm_apply_ex", "sdk_group_norm", "sdk_group_norm_finalize", "sdk_group_norm_plan", "sdk_layer_norm",
-           "sdk_attention", "sdk_attention_form", "sdk_linear_attention", "sdk_linear_attention_workspace_bytes", "sdk_linear_attention_chunks", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_ddim_step_ex", "sdk_cfg_combine", "sdk_posterior_step", "sdk_posterior_step_ex", "sdk_masked_q_sample", "sdk_concat_nchw_to_nhwc", "sdk_patch_pack", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
+           "sdk_attention", "sdk_attention_form", "sdk_linear_attention", "sdk_linear_attention_workspace_bytes", "sdk_linear_attention_chunks", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_ddim_step_ex", "sdk_multistep_step", "sdk_cfg_combine", "sdk_posterior_step", "sdk_posterior_step_ex", "sdk_masked_q_sample", "sdk_concat_nchw_to_nhwc", "sdk_patch_pack", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
            "sdk_diag_gaussian_sample", "sdk_stochastic_encode", "sdk_token_embedding", "sdk_extract_patches",
            "sdk_fold_patches", "sdk_vq_code_norms", "sdk_vq_nearest_splits", "sdk_vq_nearest", "sdk_vq_lookup", "sdk_vq_remap",
            "sdk_upsample_bilinear2x", "sdk_upsample_nearest2x_padded", "sdk_zero_border", "sdk_gelu",
@@ -206,6 +212,7 @@ def lib():
     L.sdk_ddim_xprev.argtypes = [C.POINTER(DdimArgs), vp]
     L.sdk_posterior_step.argtypes = [C.POINTER(PosteriorArgs), vp]
     L.sdk_ddim_step_ex.argtypes = [C.POINTER(DdimExArgs), vp]
+    L.sdk_multistep_step.argtypes = [C.POINTER(MultistepArgs), vp]
     L.sdk_cfg_combine.argtypes = [vp, vp, vp, i64, f32, vp]
     L.sdk_posterior_step_ex.argtypes = [C.POINTER(PosteriorExArgs), vp]
     L.sdk_masked_q_sample.argtypes = [C.POINTER(MaskedQArgs), vp]

@@ -129,6 +129,117 @@ __global__ void __launch_bounds__(256) ddim_step_kernel(sdk_ddim_ex_args ex, int
   }
 }
 
+// One element of the multistep update (sdk_multistep_step).  e / u: the model output and the unconditional one;
+// h1..h3: the history (PLMS: earlier guided ε, DPM: the previous data prediction in h1); en: the warm-up form's
+// second ε.  p0 = pred_x0, ho = the value the history receives.  Returns x_prev.
+__device__ __forceinline__ float multistep_elem(const sdk_multistep_args& m, float x, float e, float u, float h1,
+                                                float h2, float h3, float en, float& p0, float& ho) {
+  const sdk_ddim_args& a = m.step;
+  if (a.e_uncond) e = cfg_combine_elem(u, e, a.guidance);
+  if (a.v_param) {
+    const float t0 = a.v_sqrt_a * e;
+    const float t1 = a.v_sqrt_1ma * x;
+    e = t0 + t1;
+  }
+  if (m.form == SDK_MULTISTEP_DPM) {
+    const float t1 = a.sqrt_one_minus_at * e;
+    const float t2 = x - t1;
+    const float d = t2 / a.sqrt_at;
+    p0 = d, ho = d;
+    const float t3 = m.c_x * x;
+    const float t4 = m.c_0 * d;
+    float r = t3 + t4;
+    if (m.nhist) {
+      const float t5 = m.c_1 * h1;
+      r = r + t5;
+    }
+    return r;
+  }
+  ho = e;
+  float ep = e;                                   // e_t_prime of CompVis' p_sample_plms
+  if (m.form == SDK_MULTISTEP_PLMS_WARMUP) {
+    const float s = e + en;
+    ep = s / 2.f;
+  } else if (m.nhist == 1) {
+    const float t0 = 3.f * e;
+    const float t1 = t0 - h1;
+    ep = t1 / 2.f;
+  } else if (m.nhist == 2) {
+    const float t0 = 23.f * e;
+    const float t1 = 16.f * h1;
+    const float t2 = t0 - t1;
+    const float t3 = 5.f * h2;
+    const float t4 = t2 + t3;
+    ep = t4 / 12.f;
+  } else if (m.nhist == 3) {
+    const float t0 = 55.f * e;
+    const float t1 = 59.f * h1;
+    const float t2 = t0 - t1;
+    const float t3 = 37.f * h2;
+    const float t4 = t2 + t3;
+    const float t5 = 9.f * h3;
+    const float t6 = t4 - t5;
+    ep = t6 / 24.f;
+  }
+  // ddim_elem at sigma = 0 (its noise term is then +0)
+  const float t1 = a.sqrt_one_minus_at * ep;
+  const float t2 = x - t1;
+  p0 = t2 / a.sqrt_at;
+  const float dir = a.dir_coef * ep;
+  const float t3 = a.sqrt_a_prev * p0;
+  const float t4 = t3 + dir;
+  return t4 + 0.f;
+}
+
+// n4 16-byte groups (0 when a pointer is not aligned for them), then the scalar tail [4 n4, n).  Every input of
+// an element is read before any output of it is written, so hist_out may alias a history pointer and blend.out x.
+__global__ void __launch_bounds__(256) multistep_step_kernel(sdk_multistep_args m, int64_t n4) {
+  const sdk_ddim_args& a = m.step;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const bool blend = m.blend.mask != nullptr, warm = m.form == SDK_MULTISTEP_PLMS_WARMUP;
+  const int nh = warm ? 0 : m.nhist;
+  for (int64_t i = tid; i < n4; i += stride) {
+    const f4 z = {0.f, 0.f, 0.f, 0.f};
+    f4 u = z, h1 = z, h2 = z, h3 = z, en = z, b0 = z, bn = z, xp, p0, ho;
+    const f4 x = reinterpret_cast<const f4*>(a.x)[i];
+    const f4 e = reinterpret_cast<const f4*>(a.e)[i];
+    if (a.e_uncond) u = reinterpret_cast<const f4*>(a.e_uncond)[i];
+    if (nh > 0) h1 = reinterpret_cast<const f4*>(m.hist[0])[i];
+    if (nh > 1) h2 = reinterpret_cast<const f4*>(m.hist[1])[i];
+    if (nh > 2) h3 = reinterpret_cast<const f4*>(m.hist[2])[i];
+    if (warm) en = reinterpret_cast<const f4*>(m.e_next)[i];
+    if (blend) {
+      b0 = reinterpret_cast<const f4*>(m.blend.x0)[i];
+      bn = reinterpret_cast<const f4*>(m.blend.noise)[i];
+    }
+    for (int j = 0; j < 4; ++j) {
+      float p, h;
+      xp[j] = multistep_elem(m, x[j], e[j], u[j], h1[j], h2[j], h3[j], en[j], p, h);
+      p0[j] = p, ho[j] = h;
+    }
+    reinterpret_cast<f4*>(a.x_prev)[i] = xp;
+    if (a.pred_x0) reinterpret_cast<f4*>(a.pred_x0)[i] = p0;
+    if (m.hist_out) reinterpret_cast<f4*>(m.hist_out)[i] = ho;
+    if (blend) {
+      f4 o;
+      for (int j = 0; j < 4; ++j) o[j] = masked_q_elem(m.blend, 4 * i + j, b0[j], bn[j], xp[j]);
+      reinterpret_cast<f4*>(m.blend.out)[i] = o;
+    }
+  }
+  for (int64_t i = 4 * n4 + tid; i < a.n; i += stride) {
+    const float h1 = nh > 0 ? m.hist[0][i] : 0.f, h2 = nh > 1 ? m.hist[1][i] : 0.f, h3 = nh > 2 ? m.hist[2][i] : 0.f;
+    const float b0 = blend ? m.blend.x0[i] : 0.f, bn = blend ? m.blend.noise[i] : 0.f;
+    float p0, ho;
+    const float xp = multistep_elem(m, a.x[i], a.e[i], a.e_uncond ? a.e_uncond[i] : 0.f, h1, h2, h3,
+                                    warm ? m.e_next[i] : 0.f, p0, ho);
+    a.x_prev[i] = xp;
+    if (a.pred_x0) a.pred_x0[i] = p0;
+    if (m.hist_out) m.hist_out[i] = ho;
+    if (blend) m.blend.out[i] = masked_q_elem(m.blend, i, b0, bn, xp);
+  }
+}
+
 __global__ void __launch_bounds__(256) cfg_combine_kernel(const float* e_u, const float* e_c, float* out, int64_t n,
                                                           int64_t n4, float g) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -598,6 +709,38 @@ extern "C" int sdk_ddim_xprev(const sdk_ddim_args* a, sdk_stream_t stream) {
   ex.pred_x0_in = 1;
   if (!a->v_param) ex.step.x = nullptr;          // read only for the v conversion
   return launch_ddim(ex, "ddim_xprev", stream);
+}
+
+extern "C" int sdk_multistep_step(const sdk_multistep_args* m, sdk_stream_t stream) {
+  if (!m) return fail(SDK_EINVAL, "multistep_step: null pointer");
+  const sdk_ddim_args& a = m->step;
+  const sdk_masked_q_args& b = m->blend;
+  if (!a.x || !a.e || !a.x_prev) return fail(SDK_EINVAL, "multistep_step: null pointer");
+  if (a.n <= 0) return fail(SDK_EINVAL, "multistep_step: n must be positive");
+  if (a.noise || a.sigma != 0.f) return fail(SDK_EINVAL, "multistep_step: deterministic only (noise NULL, sigma 0)");
+  if (m->form < SDK_MULTISTEP_PLMS || m->form > SDK_MULTISTEP_DPM) return fail(SDK_EINVAL, "multistep_step: bad form");
+  const bool warm = m->form == SDK_MULTISTEP_PLMS_WARMUP;
+  const int max_hist = m->form == SDK_MULTISTEP_PLMS ? 3 : m->form == SDK_MULTISTEP_DPM ? 1 : 0;
+  if (m->nhist < 0 || m->nhist > max_hist)
+    return fail(SDK_EINVAL, "multistep_step: nhist must be 0..3 (PLMS), 0 (warm-up) or 0..1 (DPM)");
+  for (int k = 0; k < m->nhist; ++k)
+    if (!m->hist[k]) return fail(SDK_EINVAL, "multistep_step: nhist history pointers must be set");
+  if (warm && !m->e_next) return fail(SDK_EINVAL, "multistep_step: the warm-up form needs e_next");
+  bool vec = aligned16(a.x) && aligned16(a.e) && aligned16(a.e_uncond) && aligned16(a.x_prev) &&
+             aligned16(a.pred_x0) && aligned16(m->hist_out) && (!warm || aligned16(m->e_next));
+  for (int k = 0; k < m->nhist; ++k) vec = vec && aligned16(m->hist[k]);
+  if (b.mask) {
+    if (!b.x0 || !b.noise || !b.out) return fail(SDK_EINVAL, "multistep_step: blend needs x0, noise and out");
+    if (b.hw <= 0 || b.per_sample <= 0 || b.per_sample % b.hw || a.n % b.per_sample || b.mask_mode < 0 ||
+        b.mask_mode > 2)
+      return fail(SDK_EINVAL, "multistep_step: bad blend geometry (n = batch * per_sample, per_sample = channels * hw)");
+    vec = vec && aligned16(b.x0) && aligned16(b.noise) && aligned16(b.out);
+  }
+  const int64_t n4 = vec ? a.n / 4 : 0;
+  const int64_t items = std::max<int64_t>(n4, a.n - 4 * n4);
+  const int blocks = (int)std::min<int64_t>((items + 255) / 256, 2048);
+  hipLaunchKernelGGL(multistep_step_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *m, n4);
+  return check_launch("multistep_step");
 }
 
 extern "C" int sdk_cfg_combine(const float* e_uncond, const float* e_cond, float* out, int64_t n, float guidance,

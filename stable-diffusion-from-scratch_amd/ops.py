@@ -1501,6 +1501,93 @@ def ddim_xprev(pred_x0, e, sc: dict, x=None, noise=None, e_uncond=None, guidance
     return xp if xn is None else (xp, xn)
 
 
+MULTISTEP_FORMS = {"plms": _lib.MULTISTEP_PLMS, "plms_warmup": _lib.MULTISTEP_PLMS_WARMUP, "dpm": _lib.MULTISTEP_DPM}
+
+
+def multistep_step(x, e, sc: dict, form="plms", history=(), e_next=None, coefs=None, e_uncond=None, guidance=1.0,
+                   v_param=None, x_prev=None, pred_x0=None, hist_out=None, *, blend_x0=None, blend_noise=None,
+                   blend_mask=None, blend_sqrt_acp=None, blend_sqrt_1m_acp=None, x_next=None):
+    """Fused multistep update (``sdk_multistep_step``), one launch.  ``sc``: the eta = 0 scalars of
+    ``DDIMSampler.step_scalars``.  ``form`` "plms": ``history`` holds the guided ε of the previous 0-3 steps, most
+    recent first, and ``e' = e | (3e − h1)/2 | (23e − 16h1 + 5h2)/12 | (55e − 59h1 + 37h2 − 9h3)/24`` replaces ε in
+    the DDIM update; "plms_warmup": ``e' = (e + e_next)/2``; "dpm": ``coefs = (c_x, c_0, c_1)``, ``history`` the
+    previous data prediction or empty, ``x_prev = c_x·x + c_0·D (+ c_1·h1)``.  ``hist_out`` (a contiguous CUDA fp32
+    tensor of x's shape, or None) receives the guided ε (PLMS) or D (DPM) and may be one of ``history``.
+    ``e_uncond`` / ``guidance`` / ``v_param`` / ``x_prev`` / ``pred_x0`` / ``blend_*`` / ``x_next`` as in
+    ``ddim_step``.  Returns (x_prev, pred_x0), with a blend (x_prev, pred_x0, x_next)."""
+    what = "multistep_step"
+    _need_cuda(x, what, torch.float32)
+    _need_cuda(e, what, torch.float32)
+    if e.shape != x.shape:
+        raise ValueError(f"sd_amd.{what}: x {tuple(x.shape)} vs e {tuple(e.shape)}")
+    if form not in MULTISTEP_FORMS:
+        raise ValueError(f"sd_amd.{what}: form must be one of {sorted(MULTISTEP_FORMS)}, got {form!r}")
+    history = list(history)
+    most = {"plms": 3, "plms_warmup": 0, "dpm": 1}[form]
+    if len(history) > most:
+        raise ValueError(f"sd_amd.{what}: form '{form}' takes at most {most} history tensors, got {len(history)}")
+    if (form == "plms_warmup") != (e_next is not None):
+        raise ValueError(f"sd_amd.{what}: e_next goes with form 'plms_warmup' (and only with it)")
+    if (form == "dpm") != (coefs is not None):
+        raise ValueError(f"sd_amd.{what}: coefs = (c_x, c_0, c_1) goes with form 'dpm' (and only with it)")
+    x, e = x.contiguous(), e.contiguous()
+    t = _same_f32(what, x, e_uncond=e_uncond, e_next=e_next, **{f"history[{k}]": h for k, h in enumerate(history)})
+    for k, h in enumerate(history):
+        if h is None:
+            raise ValueError(f"sd_amd.{what}: history[{k}] is None")
+    outs = {"x_prev": x_prev, "pred_x0": pred_x0, "hist_out": hist_out, "x_next": x_next}
+    for k, v in outs.items():
+        if v is not None and (not torch.is_tensor(v) or v.shape != x.shape or not v.is_contiguous() or
+                              v.dtype != torch.float32 or v.device != x.device):
+            raise ValueError(f"sd_amd.{what}: {k} must be a contiguous CUDA fp32 tensor of x's shape")
+    xp = x_prev if x_prev is not None else torch.empty_like(x)
+    p0 = pred_x0 if pred_x0 is not None else torch.empty_like(x)
+    m = _lib.MultistepArgs()
+    a = m.step
+    a.x, a.e, a.x_prev, a.pred_x0 = x.data_ptr(), e.data_ptr(), xp.data_ptr(), p0.data_ptr()
+    a.e_uncond = t["e_uncond"].data_ptr() if t["e_uncond"] is not None else None
+    a.n = x.numel()
+    a.sqrt_one_minus_at, a.sqrt_at = float(sc["sqrt_one_minus_at"]), float(sc["sqrt_at"])
+    if form != "dpm":
+        if float(sc.get("sigma", 0.0)) != 0.0:
+            raise ValueError(f"sd_amd.{what}: PLMS is deterministic: the scalars must be those of eta = 0")
+        a.dir_coef, a.sqrt_a_prev = float(sc["dir_coef"]), float(sc["sqrt_a_prev"])
+    else:
+        m.c_x, m.c_0, m.c_1 = (float(c) for c in coefs)
+    a.temperature, a.guidance = 1.0, float(guidance)
+    if v_param is not None:
+        a.v_param = 1
+        a.v_sqrt_a, a.v_sqrt_1ma = float(v_param[0]), float(v_param[1])
+    m.form, m.nhist = MULTISTEP_FORMS[form], len(history)
+    for k in range(len(history)):
+        m.hist[k] = t[f"history[{k}]"].data_ptr()
+    if e_next is not None:
+        m.e_next = t["e_next"].data_ptr()
+    if hist_out is not None:
+        m.hist_out = hist_out.data_ptr()
+    if blend_mask is None:
+        if blend_x0 is not None or blend_noise is not None or x_next is not None:
+            raise ValueError(f"sd_amd.{what}: blend_x0 / blend_noise / x_next need blend_mask")
+        check(lib().sdk_multistep_step(C.byref(m), _stream()), what)
+        return xp, p0
+    if blend_x0 is None or blend_noise is None or blend_sqrt_acp is None or blend_sqrt_1m_acp is None:
+        raise ValueError(f"sd_amd.{what}: the blend needs blend_x0, blend_noise, blend_sqrt_acp and blend_sqrt_1m_acp")
+    tb = _same_f32(what, x, blend_x0=blend_x0, blend_noise=blend_noise)
+    if not torch.is_tensor(blend_mask) or not blend_mask.is_cuda or blend_mask.dtype != torch.float32 or \
+            blend_mask.device != x.device:
+        raise ValueError(f"sd_amd.{what}: blend_mask must be a CUDA fp32 tensor on {x.device}")
+    b = m.blend
+    b.mask_mode = _mask_mode(what, blend_mask, x.shape)
+    blend_mask = blend_mask.contiguous()
+    xn = x_next if x_next is not None else torch.empty_like(x)
+    b.x0, b.noise, b.mask, b.out = tb["blend_x0"].data_ptr(), tb["blend_noise"].data_ptr(), blend_mask.data_ptr(), \
+        xn.data_ptr()
+    b.n, b.per_sample, b.hw = x.numel(), x.numel() // x.shape[0], x.shape[2] * x.shape[3]
+    b.sqrt_acp, b.sqrt_1m_acp = float(blend_sqrt_acp), float(blend_sqrt_1m_acp)
+    check(lib().sdk_multistep_step(C.byref(m), _stream()), what)
+    return xp, p0, xn
+
+
 def cfg_combine(e_uncond, e_cond, guidance, out=None):
     """``e_uncond + guidance·(e_cond − e_uncond)`` (``ddim.py:178``) as a tensor: the two fp32 operations of
     the combine fused into ``ddim_step``, so ``ddim_step(x, cfg_combine(u, c, g), sc)`` has the bits of
