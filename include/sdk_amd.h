@@ -132,7 +132,9 @@ typedef struct {
 
 enum sdk_conv_act {
   SDK_ACT_NONE = 0,
-  SDK_ACT_QUICK_GELU = 1   /* x * sigmoid(1.702 x): CLIP MLP fc1 (transformers QuickGELUActivation) */
+  SDK_ACT_QUICK_GELU = 1,  /* x * sigmoid(1.702 x): CLIP MLP fc1 (transformers QuickGELUActivation) */
+  SDK_ACT_GELU = 2         /* 0.5 x (1 + erf(x / sqrt 2)): nn.GELU(), the OpenCLIP MLP c_fc; applied at the same
+                              place: after bias / row_bias, before the residual */
 };
 
 typedef struct {

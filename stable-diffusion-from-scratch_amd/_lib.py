@@ -135,7 +135,7 @@ class Resize2dArgs(C.Structure):
 
 OUT_NHWC_F16, OUT_NCHW_F32, OUT_GEGLU_F16, OUT_ROWS_F32 = 0, 1, 2, 3
 RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_BICUBIC, RESIZE_AREA = range(4)
-ACT_NONE, ACT_QUICK_GELU = 0, 1
+ACT_NONE, ACT_QUICK_GELU, ACT_GELU = 0, 1, 2
 ATTN_AUTO, ATTN_NW4, ATTN_NW8, ATTN_NW8_STAG, ATTN_QB2, ATTN_WIDE = range(6)
 MULTISTEP_PLMS, MULTISTEP_PLMS_WARMUP, MULTISTEP_DPM = range(3)      # SDK_MULTISTEP_*
 ATTN_WIDE_ROWS, ATTN_WIDE_KT = 64, 32      # SDK_ATTN_WIDE_ROWS / SDK_ATTN_WIDE_KT

@@ -39,9 +39,13 @@ __device__ __forceinline__ void ph_stamp(const Params& p, int i) {
 #endif
 }
 
-// epilogue activation (CLIP's quick_gelu x*sigmoid(1.702x), transformers activations.py QuickGELUActivation)
+// epilogue activation: CLIP's quick_gelu x*sigmoid(1.702x) (transformers activations.py QuickGELUActivation) or the
+// exact GELU of nn.GELU() (OpenCLIP's MLP) through gelu_erf, the library's one erf (common.h).  ERF = false compiles
+// the erf branch out, for a kernel whose launcher sends SDK_ACT_GELU to an instantiation of its own
+template <bool ERF = true>
 __device__ __forceinline__ float act_fn(int act, float x) {
   if (act == SDK_ACT_QUICK_GELU) return x * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * x));
+  if (ERF && act == SDK_ACT_GELU) return gelu_erf(x);
   return x;
 }
 

@@ -69,7 +69,8 @@ int build_params(const sdk_conv_args* a, Params& p, sdk_conv_plan_info* info) {
     return fail(SDK_EINVAL, "conv2d: empty output shape");
   if (!a->weight || !a->out) return fail(SDK_EINVAL, "conv2d: null weight/out");
   p = Params{};
-  if (a->act != SDK_ACT_NONE && a->act != SDK_ACT_QUICK_GELU) return fail(SDK_EINVAL, "conv2d: unknown act");
+  if (a->act != SDK_ACT_NONE && a->act != SDK_ACT_QUICK_GELU && a->act != SDK_ACT_GELU)
+    return fail(SDK_EINVAL, "conv2d: unknown act");
   if (a->act != SDK_ACT_NONE && a->out_mode == SDK_OUT_GEGLU_F16)
     return fail(SDK_EINVAL, "conv2d: act does not combine with the GEGLU epilogue");
   p.act = a->act;

@@ -84,7 +84,7 @@ __device__ __forceinline__ void transform_a(const Params& p, const RowCtx& rc, i
 // acc[i][j] (32x32 MFMA tile) element r of lane (fr = lane&31, fh = lane>>5):
 //   row = m_w + i*32 + (r&3) + 8*(r>>2) + 4*fh, col = n_w + j*32 + fr   (block-local)
 // LDS `smem` must be free (all waves past their last LDS read) on entry.
-template <int FM, int FN, int TBM, int TBN, int TNT>
+template <int FM, int FN, int TBM, int TBN, int TNT, bool ERF>
 __device__ __forceinline__ void epilogue(const Params& p, f16v (&acc)[FM][FN], half_t* smem, int m0, int n0, int m_w,
                                          int n_w, int split_idx) {
   const int tid = threadIdx.x, lane = tid & 63;
@@ -164,7 +164,7 @@ __device__ __forceinline__ void epilogue(const Params& p, f16v (&acc)[FM][FN], h
             const int m = min(m0 + rl, p.M - 1);
             v += p.row_bias[(size_t)(m / p.hw_out) * p.rb_ld + n];
           }
-          smem[rl * CLD + n_w + j * 32 + fr] = (half_t)act_fn(p.act, v);
+          smem[rl * CLD + n_w + j * 32 + fr] = (half_t)act_fn<ERF>(p.act, v);
         }
       }
     }
@@ -198,7 +198,7 @@ __device__ __forceinline__ void epilogue(const Params& p, f16v (&acc)[FM][FN], h
         const int b = m / p.hw_out;
         float v = acc[i][j][r] + bn[j];
         if (p.row_bias) v += p.row_bias[(size_t)b * p.rb_ld + n];
-        v = act_fn(p.act, v);
+        v = act_fn<ERF>(p.act, v);
         if (p.res) v += (float)p.res[(size_t)m * p.res_ld + n];
         float* out = reinterpret_cast<float*>(p.out);
         if (mode == SDK_OUT_NCHW_F32)
@@ -209,6 +209,10 @@ __device__ __forceinline__ void epilogue(const Params& p, f16v (&acc)[FM][FN], h
     }
 }
 
+// ERF (here and on the split-K reduces and the skinny kernel): the instantiation that runs SDK_ACT_GELU.  The
+// launchers send every other act to the ERF = false one, whose code is what it was before the erf branch existed:
+// the diffusion step runs these kernels with act none (profiles/act_gelu_resources.txt)
+template <bool ERF>
 __global__ void __launch_bounds__(NT, 2) conv_igemm_kernel(Params p) {
   __shared__ __attribute__((aligned(16))) half_t smem[4 * TILE_H];   // A0 A1 B0 B1 = 64 KiB
   half_t* As = smem;
@@ -305,7 +309,7 @@ __global__ void __launch_bounds__(NT, 2) conv_igemm_kernel(Params p) {
   }
 
   const int m_w = wm * 64, n_w = wn * 64;
-  epilogue<2, 2, BM, BN, NT>(p, acc, smem, m0, n0, m_w, n_w, blockIdx.y);
+  epilogue<2, 2, BM, BN, NT, ERF>(p, acc, smem, m0, n0, m_w, n_w, blockIdx.y);
 }
 
 // split-K reduce: a lane's pivot-shifted sums over its rows (registers are plentiful there)
@@ -395,6 +399,7 @@ __device__ __forceinline__ void epi_add8(const Params& p, int b, int n, float (&
   }
 }
 
+template <bool ERF>
 __global__ void __launch_bounds__(256) splitk_reduce_kernel(Params p) {
   const int groups = p.N / 8;
   const size_t total = (size_t)p.M * groups;
@@ -409,7 +414,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(Params p) {
     float bi[8], rbv[8];
     epi_add8(p, b, n, bi, rbv);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = act_fn(p.act, (v[j] + bi[j]) + rbv[j]);
+    for (int j = 0; j < 8; ++j) v[j] = act_fn<ERF>(p.act, (v[j] + bi[j]) + rbv[j]);
     if (p.out_mode == SDK_OUT_NHWC_F16) {
       h8 o;
 #pragma unroll
@@ -439,6 +444,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(Params p) {
 // grid (batch * gn_nch, ceil(N / 64)); 256 threads = 32 row lanes x 8 column octets over one chunk
 // (hw_out / gn_nch rows of one image); per-lane pivot-shifted sums, Chan merge of the 32 row lanes
 // through LDS, one (mean, M2) per chunk and channel.
+template <bool ERF>
 __global__ void __launch_bounds__(256) splitk_reduce_gn_kernel(Params p) {
   __shared__ float2 red[32][64];
   const int tc = threadIdx.x & 7, tr = threadIdx.x >> 3;
@@ -478,7 +484,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_gn_kernel(Params p) {
       if (q == 1 && !two) break;
       h8 o;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = (half_t)act_fn(p.act, (v[q][j] + bi[j]) + rbv[j]);
+      for (int j = 0; j < 8; ++j) o[j] = (half_t)act_fn<ERF>(p.act, (v[q][j] + bi[j]) + rbv[j]);
       if (p.res) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = (half_t)((float)o[j] + (float)rr[q][j]);
@@ -633,7 +639,7 @@ int launch_direct_n(const Params& p, hipStream_t s) {
 // 16x16x32 operand layout: lane l supplies A[row l%16][k 8(l/16)..+8] and B[k 8(l/16)..+8][col l%16];
 // D element i of lane l is D[4(l/16) + i][l%16].
 
-template <int MB>   // 16-row blocks
+template <int MB, bool ERF>   // 16-row blocks
 __global__ void __launch_bounds__(256) conv_skinny_kernel(Params p) {
   __shared__ float red[4][MB][4][64];
   const Seg& g = p.seg[0];
@@ -687,7 +693,7 @@ __global__ void __launch_bounds__(256) conv_skinny_kernel(Params p) {
     float v = red[0][mb][i][l] + red[1][mb][i][l] + red[2][mb][i][l] + red[3][mb][i][l];
     if (p.bias) v += p.bias[n];
     if (p.row_bias) v += p.row_bias[(size_t)(row / p.hw_out) * p.rb_ld + n];
-    v = act_fn(p.act, v);
+    v = act_fn<ERF>(p.act, v);
     if (p.res) v += (float)p.res[(size_t)row * p.res_ld + n];
     if (p.out_mode == SDK_OUT_ROWS_F32)
       reinterpret_cast<float*>(p.out)[(size_t)row * p.out_ld + n] = v;
@@ -701,19 +707,26 @@ __global__ void __launch_bounds__(256) conv_skinny_kernel(Params p) {
 namespace conv {
 
 int launch_igemm(const Params& p, hipStream_t s) {
-  hipLaunchKernelGGL(conv_igemm_kernel, dim3(p.tiles_m * p.tiles_n, p.split), dim3(NT), 0, s, p);
+  const dim3 grid(p.tiles_m * p.tiles_n, p.split);
+  if (p.act == SDK_ACT_GELU) hipLaunchKernelGGL(conv_igemm_kernel<true>, grid, dim3(NT), 0, s, p);
+  else hipLaunchKernelGGL(conv_igemm_kernel<false>, grid, dim3(NT), 0, s, p);
   return check_launch("conv_igemm");
 }
 
 int launch_splitk_reduce(const Params& p, hipStream_t s) {
   const size_t total = (size_t)p.M * (p.N / 8);
   int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, p);
+  if (p.act == SDK_ACT_GELU)
+    hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3(blocks), dim3(256), 0, s, p);
+  else
+    hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3(blocks), dim3(256), 0, s, p);
   return check_launch("splitk_reduce");
 }
 
 int launch_splitk_reduce_gn(const Params& p, hipStream_t s) {
-  hipLaunchKernelGGL(splitk_reduce_gn_kernel, dim3(p.batch * p.gn_nch, (p.N + 63) / 64), dim3(256), 0, s, p);
+  const dim3 grid(p.batch * p.gn_nch, (p.N + 63) / 64);
+  if (p.act == SDK_ACT_GELU) hipLaunchKernelGGL(splitk_reduce_gn_kernel<true>, grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(splitk_reduce_gn_kernel<false>, grid, dim3(256), 0, s, p);
   return check_launch("splitk_reduce_gn");
 }
 
@@ -721,11 +734,17 @@ int launch_direct(const Params& p, hipStream_t s) {
   return p.N <= 4 ? launch_direct_n<4>(p, s) : launch_direct_n<8>(p, s);
 }
 
-int launch_skinny(const Params& p, hipStream_t s) {
+template <bool ERF>
+static void launch_skinny_rows(const Params& p, hipStream_t s) {
   const dim3 grid((p.N + 15) / 16);
-  if (p.M <= 16) hipLaunchKernelGGL(conv_skinny_kernel<1>, grid, dim3(256), 0, s, p);
-  else if (p.M <= 32) hipLaunchKernelGGL(conv_skinny_kernel<2>, grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(conv_skinny_kernel<4>, grid, dim3(256), 0, s, p);
+  if (p.M <= 16) hipLaunchKernelGGL((conv_skinny_kernel<1, ERF>), grid, dim3(256), 0, s, p);
+  else if (p.M <= 32) hipLaunchKernelGGL((conv_skinny_kernel<2, ERF>), grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((conv_skinny_kernel<4, ERF>), grid, dim3(256), 0, s, p);
+}
+
+int launch_skinny(const Params& p, hipStream_t s) {
+  if (p.act == SDK_ACT_GELU) launch_skinny_rows<true>(p, s);
+  else launch_skinny_rows<false>(p, s);
   return check_launch("conv_skinny");
 }
 

@@ -310,21 +310,33 @@ class BasicTransformerBlock(nn.Module):
 
 
 class SpatialTransformer(nn.Module):
-    """Reference ``attention.py:303-363``: GN(eps 1e-6) → proj_in 1x1 → blocks → proj_out 1x1 → + x."""
+    """Reference ``attention.py:303-363``: GN(eps 1e-6) → proj_in 1x1 → blocks → proj_out 1x1 → + x.
+    ``use_linear`` (Stability's SD-2 ``ldm/modules/attention.py``, the UNet's ``use_linear_in_transformer``): the two
+    projections are ``nn.Linear`` with 2-D weights.  On tokens a 1x1 conv and a Linear are the same GEMM, so only the
+    parameter shapes differ: ``_prepare`` packs either form into the same objects and ``_run`` is the same."""
 
-    def __init__(self, in_channels, n_heads, d_head, depth=1, dropout=0., context_dim=None):
+    def __init__(self, in_channels, n_heads, d_head, depth=1, dropout=0., context_dim=None, use_linear=False):
         super().__init__()
         self.in_channels = in_channels
         inner_dim = n_heads * d_head
         self.inner_dim = inner_dim
+        self.use_linear = use_linear
         self.norm = Normalize(in_channels)
-        self.proj_in = nn.Conv2d(in_channels, inner_dim, kernel_size=1, stride=1, padding=0)
+        if use_linear:
+            self.proj_in = nn.Linear(in_channels, inner_dim)
+        else:
+            self.proj_in = nn.Conv2d(in_channels, inner_dim, kernel_size=1, stride=1, padding=0)
         self.transformer_blocks = nn.ModuleList(
             [BasicTransformerBlock(inner_dim, n_heads, d_head, dropout=dropout, context_dim=context_dim)
              for _ in range(depth)])
-        self.proj_out = zero_module(nn.Conv2d(inner_dim, in_channels, kernel_size=1, stride=1, padding=0))
+        if use_linear:
+            # Stability's argument order (in_channels, inner_dim); the two are equal in every UNet
+            self.proj_out = zero_module(nn.Linear(in_channels, inner_dim))
+        else:
+            self.proj_out = zero_module(nn.Conv2d(inner_dim, in_channels, kernel_size=1, stride=1, padding=0))
 
     def _prepare(self, dev):
+        # PackedConv / PackedTokenLinear take [N, K] and [N, K, 1, 1] weights alike
         prep_norm(self.norm, dev)
         self._pc_in = ops.PackedConv([(self.proj_in.weight, self.in_channels)], self.proj_in.bias, device=dev)
         self._ptl_in = (ops.PackedTokenLinear(self.proj_in.weight, self.proj_in.bias, dev)

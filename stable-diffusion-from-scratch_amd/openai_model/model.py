@@ -188,7 +188,7 @@ class UNetModel(PackedOwner, nn.Module):
                  num_classes=None, use_checkpoint=False, use_fp16=False, num_heads=-1, num_head_channels=-1,
                  num_heads_upsample=-1, use_scale_shift_norm=False, resblock_updown=False,
                  use_new_attention_order=False, use_spatial_transformer=False, transformer_depth=1,
-                 context_dim=None, n_embed=None, legacy=True):
+                 context_dim=None, n_embed=None, legacy=True, use_linear_in_transformer=False):
         super().__init__()
         if use_spatial_transformer:
             assert context_dim is not None, "use_spatial_transformer needs context_dim"
@@ -236,7 +236,8 @@ class UNetModel(PackedOwner, nn.Module):
         def attn_layer(ch, heads_for_attnblock):
             dim_head = geom(ch)
             if use_spatial_transformer:
-                return SpatialTransformer(ch, num_heads, dim_head, depth=transformer_depth, context_dim=context_dim)
+                return SpatialTransformer(ch, num_heads, dim_head, depth=transformer_depth, context_dim=context_dim,
+                                          use_linear=use_linear_in_transformer)
             return AttentionBlock(ch, use_checkpoint=use_checkpoint,
                                   num_heads=num_heads if heads_for_attnblock is None else heads_for_attnblock,
                                   num_head_channels=dim_head, use_new_attention_order=use_new_attention_order)

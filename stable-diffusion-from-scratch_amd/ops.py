@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (ACT_NONE, ACT_QUICK_GELU, AttentionArgs, XAttnArgs, XAttnLnArgs, FfArgs, TokenLinearArgs, ConvArgs, ConvPlanInfo, GroupNormArgs,
+from ._lib import (ACT_NONE, ACT_QUICK_GELU, ACT_GELU, AttentionArgs, XAttnArgs, XAttnLnArgs, FfArgs, TokenLinearArgs, ConvArgs, ConvPlanInfo, GroupNormArgs,
                    OUT_GEGLU_F16, OUT_NCHW_F32, OUT_NHWC_F16, OUT_ROWS_F32, check, lib)
 
 BK = 64          # K tile of the conv kernel (packed weight column padding)
@@ -609,11 +609,11 @@ def conv2d(pc: PackedConv, x, *, ksize=None, stride=1, pad=None, pad_end=0, upsa
 
 
 def linear(pc: PackedConv, x2d, *, silu=False, residual=None, out_mode=OUT_NHWC_F16, out=None, bias=True,
-           act=ACT_NONE, n_img=None, plan_out=None):
+           act=ACT_NONE, n_img=None, plan_out=None, split_k=None):
     """Token GEMM: x2d [M, K] fp16 → [M, N]; a 1x1 conv over an M x 1 image.  ``silu`` applies to
-    the input (prologue), ``act`` to the output (epilogue, before the residual).  ``n_img``: rows per
-    image, for a ``PerImageWeights`` pc (the GEMM runs as M / n_img images of n_img x 1).
-    ``plan_out``: as for ``conv2d``."""
+    the input (prologue), ``act`` (``ACT_QUICK_GELU`` / ``ACT_GELU``) to the output (epilogue, before the
+    residual).  ``n_img``: rows per image, for a ``PerImageWeights`` pc (the GEMM runs as M / n_img images of
+    n_img x 1).  ``plan_out`` / ``split_k``: as for ``conv2d``."""
     _claim(out)
     M = x2d.shape[0]
     nb, rows = (1, M) if n_img is None else (M // n_img, n_img)
@@ -625,7 +625,8 @@ def linear(pc: PackedConv, x2d, *, silu=False, residual=None, out_mode=OUT_NHWC_
         x4 = x2d.as_strided((nb, rows, 1, x2d.shape[1]), (rows * x2d.stride(0), x2d.stride(0), x2d.stride(0), 1))
     res4 = residual.view(nb, rows, 1, residual.shape[-1]) if residual is not None else None
     y = conv2d(pc, x4, ksize=1, pad=0, silu=silu, residual=res4, out_mode=out_mode, bias=bias,
-               out=None if out is None else out.view(nb, rows, 1, out.shape[-1]), act=act, plan_out=plan_out)
+               out=None if out is None else out.view(nb, rows, 1, out.shape[-1]), act=act, plan_out=plan_out,
+               split_k=split_k)
     return y.view(M, y.shape[-1])
 
 
