@@ -422,6 +422,31 @@ int sdk_token_linear(const sdk_token_linear_args* a, sdk_stream_t stream);
 int sdk_token_linear_ln(const sdk_token_linear_args* a, const float* gamma, const float* beta, float eps,
                         void* out_ln, int32_t out_ln_ld, sdk_stream_t stream);
 
+/* ---------------------------------------------------------------- SpatialTransformer entry, chained
+ * The entry of a 320-channel SpatialTransformer in one launch (csrc/conv_rowpanel.hip, proj_norm_qkv_kernel):
+ *   tok = proj_in(xn),  qkv = [to_q | to_k | to_v](LayerNorm(tok)),   xn = x, or (half)(x * scale + shift)
+ * (openai_model/attention.py:328-330 then :251 and :96-99).  tok and qkv carry the bits of sdk_group_norm (no SiLU)
+ * -> sdk_token_linear_ln -> sdk_conv2d on the q|k|v weight; the GroupNorm output and LayerNorm(tok) are never
+ * written.  x [rows, x_ld], tok [rows, tok_ld], qkv [rows, qkv_ld]: fp16, 16-B aligned, strides multiples of 8;
+ * neither output may overlap an input or the other output.
+ * w: fp16 [1280][320], bias: fp32 [1280] — proj_in's rows first, PERMUTED: packed row 160 c + 16 nb + 4 cg + q
+ * (c < 2, nb < 10, cg < 4, q < 4) holds output channel 32 (g / 2) + 8 cg + 4 (g % 2) + q with g = 10 c + nb; then
+ * the 960 q|k|v rows in order (their bias entries zero where the projections have none).
+ * gamma / beta: fp32 [320] of the LayerNorm.  gn_scale / gn_shift: NULL, or the fp32 [rows / hw][320] affine of
+ * sdk_group_norm_affine with hw = rows per image (rows % hw == 0).  in_features / features / qkv_features must be
+ * 320 / 320 / 960 (sdk_proj_norm_qkv_supported).
+ */
+typedef struct {
+  const void* x; const float* gn_scale; const float* gn_shift; const void* w; const float* bias;
+  const float* gamma; const float* beta; void* tok; void* qkv;
+  int32_t x_ld, tok_ld, qkv_ld, rows, hw;
+  int32_t in_features, features, qkv_features;
+  float eps;
+} sdk_proj_norm_qkv_args;
+
+int sdk_proj_norm_qkv_supported(int32_t in_features, int32_t features, int32_t qkv_features);
+int sdk_proj_norm_qkv(const sdk_proj_norm_qkv_args* a, sdk_stream_t stream);
+
 /* ---------------------------------------------------------------- sampler / glue
  * DDIM update (DDIM/ddim.py:194-204 == ldm/diffusion/ddim.py:197-205), fp32,
  * evaluated op by op without contraction so it is bit-identical to torch's CPU

@@ -86,6 +86,12 @@ class TokenLinearArgs(C.Structure):
                 ("out_ld", i32), ("rows", i32), ("in_features", i32), ("out_features", i32)]
 
 
+class ProjNormQkvArgs(C.Structure):
+    _fields_ = [("x", vp), ("gn_scale", vp), ("gn_shift", vp), ("w", vp), ("bias", vp), ("gamma", vp), ("beta", vp),
+                ("tok", vp), ("qkv", vp), ("x_ld", i32), ("tok_ld", i32), ("qkv_ld", i32), ("rows", i32), ("hw", i32),
+                ("in_features", i32), ("features", i32), ("qkv_features", i32), ("eps", f32)]
+
+
 class DdimArgs(C.Structure):
     _fields_ = [("x", vp), ("e", vp), ("e_uncond", vp), ("noise", vp), ("x_prev", vp), ("pred_x0", vp),
                 ("n", i64), ("sqrt_one_minus_at", f32), ("sqrt_at", f32), ("dir_coef", f32), ("sqrt_a_prev", f32),
@@ -144,7 +150,7 @@ GN_STATS = ("given", "slice", "chunked", "parts")              # SDK_GN_STATS_*
 GN_APPLY = ("none", "in_stats", "flat", "row", "stride")       # SDK_GN_APPLY_*
 
 EXPORTS = ["sdk_conv2d_plan", "sdk_conv2d", "sdk_group_norm_workspace", "sdk_group_norm_affine", "sdk_group_norm_apply", "sdk_group_norm_apply_padded", "sdk_group_norm_apply_ex", "sdk_group_norm", "sdk_group_norm_finalize", "sdk_group_norm_plan", "sdk_layer_norm",
-           "sdk_attention", "sdk_attention_form", "sdk_linear_attention", "sdk_linear_attention_workspace_bytes", "sdk_linear_attention_chunks", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_ddim_step_ex", "sdk_multistep_step", "sdk_cfg_combine", "sdk_posterior_step", "sdk_posterior_step_ex", "sdk_masked_q_sample", "sdk_concat_nchw_to_nhwc", "sdk_patch_pack", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
+           "sdk_attention", "sdk_attention_form", "sdk_linear_attention", "sdk_linear_attention_workspace_bytes", "sdk_linear_attention_chunks", "sdk_cross_attention_block_supported", "sdk_xattn_pack_weight", "sdk_cross_attention_block", "sdk_cross_attention_block_ln", "sdk_segment_softmax", "sdk_ff_supported", "sdk_ff_packed_bytes", "sdk_ff_pack", "sdk_feed_forward", "sdk_token_linear_supported", "sdk_token_linear", "sdk_token_linear_ln", "sdk_proj_norm_qkv_supported", "sdk_proj_norm_qkv", "sdk_ddim_step", "sdk_ddim_xprev", "sdk_ddim_step_ex", "sdk_multistep_step", "sdk_cfg_combine", "sdk_posterior_step", "sdk_posterior_step_ex", "sdk_masked_q_sample", "sdk_concat_nchw_to_nhwc", "sdk_patch_pack", "sdk_ddpm_step", "sdk_timestep_embedding", "sdk_nchw_to_nhwc",
            "sdk_diag_gaussian_sample", "sdk_stochastic_encode", "sdk_token_embedding", "sdk_extract_patches",
            "sdk_fold_patches", "sdk_vq_code_norms", "sdk_vq_nearest_splits", "sdk_vq_nearest", "sdk_vq_lookup", "sdk_vq_remap",
            "sdk_upsample_bilinear2x", "sdk_upsample_nearest2x_padded", "sdk_zero_border", "sdk_gelu",
@@ -208,6 +214,8 @@ def lib():
     L.sdk_token_linear_supported.argtypes = [i32, i32]
     L.sdk_token_linear.argtypes = [C.POINTER(TokenLinearArgs), vp]
     L.sdk_token_linear_ln.argtypes = [C.POINTER(TokenLinearArgs), vp, vp, f32, vp, i32, vp]
+    L.sdk_proj_norm_qkv_supported.argtypes = [i32, i32, i32]
+    L.sdk_proj_norm_qkv.argtypes = [C.POINTER(ProjNormQkvArgs), vp]
     L.sdk_ddim_step.argtypes = [C.POINTER(DdimArgs), vp]
     L.sdk_ddim_xprev.argtypes = [C.POINTER(DdimArgs), vp]
     L.sdk_posterior_step.argtypes = [C.POINTER(PosteriorArgs), vp]

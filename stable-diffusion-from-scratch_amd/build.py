@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsdk_amd.so")
-SOURCES = ["norm.hip", "attention.hip", "attention_wide.hip", "linattn.hip", "sampler.hip", "xattn.hip", "ff.hip", "token.hip", "vq.hip", "cond.hip", "probe.hip"]
+SOURCES = ["norm.hip", "attention.hip", "attention_wide.hip", "linattn.hip", "sampler.hip", "xattn.hip", "ff.hip", "token.hip", "proj_qkv.hip", "vq.hip", "cond.hip", "probe.hip"]
 # the conv units: the host planner, the small kernels, and the tile kernels, whose one small source is compiled
 # once per part (-DSDK_CONV_PART=k expands the launcher of that part's variant rows) so the objects build in parallel
 CONV_TILE_PARTS = 5
@@ -30,7 +30,7 @@ def _units():
 def _deps(src: str, csrc: str):
     """The files an object of ``src`` is rebuilt for: every conv unit depends on every conv*.h of ``csrc``."""
     headers = [os.path.join(csrc, "common.h"), os.path.join(HERE, "..", "include", "sdk_amd.h")]
-    if src.startswith("conv"):
+    if src.startswith("conv") or src == "proj_qkv.hip":     # proj_qkv.hip reads conv_cfg.h / conv_device.h
         headers += sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.startswith("conv") and f.endswith(".h"))
     return [os.path.join(csrc, src)] + headers
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -48,8 +48,9 @@ EXTRA = {"attention.hip": ["-mno-amdgpu-ieee", "-fno-honor-nans"],
 REMARK = "-Rpass-analysis=kernel-resource-usage"
 # the wide attention kernel (attention_wide.hip) sits at 168 VGPRs with one workgroup per CU: a spill would put
 # scratch round trips into every 32-key tile, so it must build without scratch too; the row-panel conv kernel
-# (conv_rowpanel.hip) holds 160 long-lived registers per lane at two waves per SIMD: a spill there lands in its MFMA loop
-NO_SCRATCH = re.compile(r"token_linear320_kernel|attn_wide_kernel|conv_rowpanel_kernel")
+# (conv_rowpanel.hip) holds 160 long-lived registers per lane at two waves per SIMD: a spill there lands in its MFMA loop;
+# its chained form (proj_qkv.hip) peaks at 220 of them and counts its own stores the same way
+NO_SCRATCH = re.compile(r"token_linear320_kernel|attn_wide_kernel|conv_rowpanel_kernel|proj_norm_qkv_kernel")
 WARN_SCRATCH = re.compile(r"conv_glds_kernel|conv_ph_kernel|ff_geglu_kernel|xattn_block_kernel|attn_fwd_kernel|vq_nearest_")
 _RES = re.compile(r"remark: (?:Function Name: (\S+)|\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+))")
 

@@ -39,6 +39,14 @@ inline int ensure_dyn_lds(const void* fn, int bytes, std::atomic<unsigned long l
 }
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
+// The GroupNorm transform silu?(x*sc + sh) in fp32, written once for every apply form of norm.hip (the avg-pool
+// resample sums four of these before it rounds) and for the GEMM prologue that applies it to its own operand
+// (conv_rowpanel.hip): under the library's one contraction setting the same expression gives the same bits
+__device__ __forceinline__ float gn_act(float x, float sc, float sh, int silu) {
+  float t = x * sc + sh;
+  if (silu) t = t * __builtin_amdgcn_rcpf(1.0f + __expf(-t));
+  return t;
+}
 // erf by Abramowitz & Stegun 7.1.26 (|error| < 1.5e-7 in exact arithmetic): one rcp + one exp + 5 FMAs
 // instead of the libm erff branches.  The fp32 roundings of 1 - y e^(-x^2) and of gelu_erf's 1 + erf come on
 // top: as far as an fp16 result shows it, gelu_erf's erf-equivalent error E (|gelu error| <= 0.5 |x| E)
@@ -142,10 +150,26 @@ __device__ __forceinline__ void ln_row_stats(const h8 (&v)[MAXV], int cols, floa
 // normalises 16 rows with the instructions a wave-per-row layout spends on ~3.  Shared by
 // layer_norm_quad_kernel (norm.hip), the cross-attention block's fused norm2 / norm3 (xattn.hip) and
 // token_linear_ln (token.hip), so all produce the same bits.  Pivot x0 = the row's first element.
-template <int CPL>
-__device__ __forceinline__ void ln_quad_stats(const h8 (&v)[CPL], float eps, float& mean, float& rstd) {
+// Where a row's four lanes sit is the exchange step X: pivot() brings the q = 0 lane's value to all four, x1() / x2()
+// the value of the lane with q ^ 1 / q ^ 2.  The in-lane sums, the order of the two cross-lane adds and the closing
+// arithmetic are this one text for every placement, so every placement gives the same bits.
+struct LnQuadLanes {   // lanes 4 r .. 4 r + 3 (q = lane & 3)
+  static __device__ __forceinline__ float pivot(float x) { return dpp_f<0x00>(x); }   // quad_perm [0,0,0,0]
+  static __device__ __forceinline__ float x1(float x) { return dpp_f<0xB1>(x); }      // quad_perm [1,0,3,2]
+  static __device__ __forceinline__ float x2(float x) { return dpp_f<0x4E>(x); }      // quad_perm [2,3,0,1]
+};
+struct LnFragLanes {   // lanes r, r + 16, r + 32, r + 48 (q = lane >> 4): the MFMA B-operand fragments of 16 rows
+  static __device__ __forceinline__ float from(float x, int l) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * l, __builtin_bit_cast(int, x)));
+  }
+  static __device__ __forceinline__ float pivot(float x) { return from(x, threadIdx.x & 15); }
+  static __device__ __forceinline__ float x1(float x) { return from(x, (threadIdx.x & 63) ^ 16); }
+  static __device__ __forceinline__ float x2(float x) { return from(x, (threadIdx.x & 63) ^ 32); }
+};
+template <int CPL, class X>
+__device__ __forceinline__ void ln_quad_stats_on(const h8 (&v)[CPL], float eps, float& mean, float& rstd) {
 #pragma clang fp contract(off)
-  const float x0 = dpp_f<0x00>((float)v[0][0]);    // quad_perm [0,0,0,0]
+  const float x0 = X::pivot((float)v[0][0]);
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int i = 0; i < CPL; ++i)
@@ -155,15 +179,19 @@ __device__ __forceinline__ void ln_quad_stats(const h8 (&v)[CPL], float eps, flo
       s1 += d;
       s2 = __builtin_fmaf(d, d, s2);
     }
-  s1 += dpp_f<0xB1>(s1);
-  s2 += dpp_f<0xB1>(s2);
-  s1 += dpp_f<0x4E>(s1);
-  s2 += dpp_f<0x4E>(s2);
+  s1 += X::x1(s1);
+  s2 += X::x1(s2);
+  s1 += X::x2(s1);
+  s2 += X::x2(s2);
   const float inv_n = 1.f / (32 * CPL);
   const float dm = s1 * inv_n;
   const float var = fmaxf(__builtin_fmaf(-dm, dm, s2 * inv_n), 0.f);
   mean = x0 + dm;
   rstd = rsqrtf(var + eps);
+}
+template <int CPL>
+__device__ __forceinline__ void ln_quad_stats(const h8 (&v)[CPL], float eps, float& mean, float& rstd) {
+  ln_quad_stats_on<CPL, LnQuadLanes>(v, eps, mean, rstd);
 }
 
 // normalised chunk k of a row: gamma / beta (fp32) from LDS (`gb`: gamma[C] then beta[C])

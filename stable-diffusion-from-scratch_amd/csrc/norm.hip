@@ -53,13 +53,7 @@ __device__ __forceinline__ void gn_load8(const float* p, float o[8]) {
   for (int j = 0; j < 4; ++j) { o[j] = a[j]; o[4 + j] = b[j]; }
 }
 
-// silu?(x*sc + sh) in fp32 (the avg-pool resample sums four of these before it rounds)
-__device__ __forceinline__ float gn_act(float x, float sc, float sh, int silu) {
-  float t = x * sc + sh;
-  if (silu) t = t * __builtin_amdgcn_rcpf(1.0f + __expf(-t));
-  return t;
-}
-
+// (gn_act, silu?(x*sc + sh) in fp32, is in common.h)
 __device__ __forceinline__ h8 gn_act8(h8 v, const float sc[8], const float sh[8], int silu) {
   h8 o;
 #pragma unroll

@@ -13,6 +13,8 @@ checkpoints and ``Diffusion/config.yaml`` params load unchanged.  Execution
   GEGLU projection fuses ``x * gelu(gate)`` in its epilogue;
 * the SpatialTransformer GroupNorm is one ``sdk_group_norm`` call (its statistics merged from the
   producing conv's epilogue partials, then one apply pass) in front of the proj_in GEMM;
+* at the 320-channel level that GroupNorm's apply pass, proj_in, the first block's norm1 and its q|k|v GEMM are one
+  launch (``ops.proj_norm_qkv``) where the row count fills the CUs;
 * at the 320-channel (and small 640-channel) levels the cross-attention block — norm2, to_q, the
   attention over the cached context K/V, to_out + residual, norm3 — is one kernel (xattn.hip).
 """
@@ -25,7 +27,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..packing import f32, gn_norm, prep_norm
+from ..packing import f32, gn_norm, gn_scale_shift, prep_norm
 from .utils import conv_nd, normalization, zero_module
 
 
@@ -80,6 +82,13 @@ FUSED_FF = os.environ.get("SD_AMD_FUSED_FF") != "0"
 # same-box A/B: UNet step 19.58 -> 19.44 ms (profiles/r4_token_linear_ab.txt).  SD_AMD_TOKEN_LINEAR=0
 # keeps the tiled GEMM + separate LayerNorm
 TOKEN_LINEAR = os.environ.get("SD_AMD_TOKEN_LINEAR", "1") != "0"
+# The 320-channel SpatialTransformer's entry — GroupNorm apply, proj_in, the first block's norm1 and its q|k|v
+# projection — as one row-panel launch (ops.proj_norm_qkv, csrc/conv_rowpanel.hip: the GroupNorm output and
+# norm1(tok) never cross HBM; the same bits).  SD_AMD_PROJ_QKV_CHAIN=0 restores the three launches, =xn keeps the
+# GroupNorm apply pass and chains only the rest (A/B of the stages)
+_CHAIN_ENV = os.environ.get("SD_AMD_PROJ_QKV_CHAIN", "1")
+PROJ_QKV_CHAIN = _CHAIN_ENV != "0"
+PROJ_QKV_CHAIN_GN = _CHAIN_ENV != "xn"
 
 
 class ReassocContext:
@@ -190,11 +199,14 @@ class CrossAttention(nn.Module):
             return ops.PerImageWeights(w1, H * L), ops.PerImageWeights(w2, Co, self._bo32)
         return ReassocContext(kv, H, L, B, build)
 
-    def _run(self, t, residual, B, N, kv=None, Lc=None):
+    def _run(self, t, residual, B, N, kv=None, Lc=None, qkv=None):
+        """``qkv``: the self-attention's q|k|v projection of ``t`` when the producer of ``t`` already ran it
+        (``ops.proj_norm_qkv``); ``t`` is then not needed and may be None."""
         inner = self.heads * self.dim_head
         if kv is None:
             if self.self_attn:
-                qkv = ops.linear(self._pc_qkv, t)
+                if qkv is None:
+                    qkv = ops.linear(self._pc_qkv, t)
                 q, k, v, nk = qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], N
             else:   # context defaults to x (reference: default(context, x)) — only legal if dims match
                 q = ops.linear(self._pc_q, t)
@@ -287,11 +299,12 @@ class BasicTransformerBlock(nn.Module):
         for n in (self.norm1, self.norm2, self.norm3):
             prep_norm(n, dev)
 
-    def _run(self, tok, B, N, kv=None, Lc=None, t=None):
-        """``t``: norm1(tok) when the producer of ``tok`` emitted it (token_linear with a norm)."""
-        if t is None:
+    def _run(self, tok, B, N, kv=None, Lc=None, t=None, qkv=None):
+        """``t``: norm1(tok) when the producer of ``tok`` emitted it (token_linear with a norm); ``qkv``: attn1's
+        q|k|v projection of norm1(tok) when the producer ran that too (proj_norm_qkv)."""
+        if t is None and qkv is None:
             t = ops.layer_norm(tok, self.norm1._g, self.norm1._b, self.norm1.eps)
-        tok = self.attn1._run(t, tok, B, N)
+        tok = self.attn1._run(t, tok, B, N, qkv=qkv)
         a2 = self.attn2
         if (kv is not None and FUSED_XATTN_NORMS and tok.stride(-1) == 1
                 and _use_fused_xattn(a2.heads * a2.dim_head, a2.dim_head, Lc, N, B)):
@@ -344,12 +357,32 @@ class SpatialTransformer(nn.Module):
         self._pc_out = ops.PackedConv([(self.proj_out.weight, self.inner_dim)], self.proj_out.bias, device=dev)
         for blk in self.transformer_blocks:
             blk._prepare(dev)
+        # proj_in + the first block's norm1 + its q|k|v as one packed weight (replaced with the others on a repack)
+        self._ppq = None
+        if len(self.transformer_blocks) and self._ptl_in is not None:
+            a1 = self.transformer_blocks[0].attn1
+            if ops.proj_norm_qkv_supported(self.in_channels, self.inner_dim, 3 * a1.heads * a1.dim_head):
+                wqkv = torch.cat([a1.to_q.weight, a1.to_k.weight, a1.to_v.weight], 0)
+                self._ppq = ops.PackedProjQkv(self.proj_in.weight, self.proj_in.bias, wqkv, dev)
 
     def context_kv(self, ctx2d, L=None):
         return [blk.attn2.context_kv(ctx2d, L) for blk in self.transformer_blocks]
 
     def _run(self, x, kvs=None, Lc=None):
         B, H, W, Cc = x.shape
+        if (PROJ_QKV_CHAIN and TOKEN_LINEAR and self._ppq is not None and x.is_contiguous()
+                and ops.proj_qkv_chain_fills(B * H * W, ops.cu_count(x.device))):
+            # the whole entry in one launch: GroupNorm affine on the way in, proj_in, norm1, q|k|v
+            n1 = self.transformer_blocks[0].norm1
+            if PROJ_QKV_CHAIN_GN:
+                tok, qkv = ops.proj_norm_qkv(self._ppq, x.view(B * H * W, Cc), (n1._g, n1._b, n1.eps),
+                                             gn=gn_scale_shift(self.norm, x), hw=H * W)
+            else:
+                xn = gn_norm(self.norm, x, silu=False)
+                tok, qkv = ops.proj_norm_qkv(self._ppq, xn.view(B * H * W, Cc), (n1._g, n1._b, n1.eps))
+            for i, blk in enumerate(self.transformer_blocks):
+                tok = blk._run(tok, B, H * W, None if kvs is None else kvs[i], Lc, qkv=qkv if i == 0 else None)
+            return ops.conv2d(self._pc_out, tok.view(B, H, W, self.inner_dim), residual=x, gn_stats=True)
         # GN materialised by one streaming pass, then the LDS-DMA GEMM (a GN prologue forces the
         # register-staged kernel: 150-190 TF/s on these shapes vs 330-650 for apply + DMA GEMM)
         xn = gn_norm(self.norm, x, silu=False)

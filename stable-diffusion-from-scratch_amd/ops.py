@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (ACT_NONE, ACT_QUICK_GELU, ACT_GELU, AttentionArgs, XAttnArgs, XAttnLnArgs, FfArgs, TokenLinearArgs, ConvArgs, ConvPlanInfo, GroupNormArgs,
+from ._lib import (ACT_NONE, ACT_QUICK_GELU, ACT_GELU, AttentionArgs, XAttnArgs, XAttnLnArgs, FfArgs, TokenLinearArgs, ProjNormQkvArgs, ConvArgs, ConvPlanInfo, GroupNormArgs,
                    OUT_GEGLU_F16, OUT_NCHW_F32, OUT_NHWC_F16, OUT_ROWS_F32, check, lib)
 
 BK = 64          # K tile of the conv kernel (packed weight column padding)
@@ -1292,6 +1292,124 @@ def token_linear(pk: PackedTokenLinear, x, residual=None, out=None, norm=None):
     if PROFILER.active:
         PROFILER.end()
     return out if norm is None else (out, out_ln)
+
+
+# ------------------------------------------------------------ SpatialTransformer entry, chained (sdk_proj_norm_qkv)
+PROJ_QKV_C, PROJ_QKV_N = 320, 960
+PROJ_QKV_PANEL = 256         # rows a workgroup of the chained kernel (and of the row-panel kernel) owns
+
+
+def proj_qkv_perm():
+    """``perm[p]`` = the proj_in output channel whose weight row and bias sit at packed position ``p`` (int64 [320]):
+    ``p = 160 c + 16 nb + 4 cg + q`` holds channel ``32 (g // 2) + 8 cg + 4 (g % 2) + q`` with ``g = 10 c + nb`` — the
+    order in which a 16x16 MFMA accumulator block (one token and four channels per lane) is, once rounded to fp16,
+    half of the same lane's eight-channel operand fragment of the next GEMM."""
+    p = torch.arange(PROJ_QKV_C)
+    c, r = p // 160, p % 160
+    nb, cg, q = r // 16, (r % 16) // 4, r % 4
+    g = 10 * c + nb
+    return 32 * (g // 2) + 8 * cg + 4 * (g % 2) + q
+
+
+def proj_qkv_pack(w_in, b_in, w_qkv, b_qkv=None):
+    """(weight fp32 [1280, 320], bias fp32 [1280]) of the chained kernel: proj_in's rows permuted by ``proj_qkv_perm``,
+    then the q|k|v rows (bias zero where the projections have none)."""
+    w_in = w_in.detach().float().reshape(w_in.shape[0], -1)
+    w_qkv = w_qkv.detach().float().reshape(w_qkv.shape[0], -1)
+    if tuple(w_in.shape) != (PROJ_QKV_C, PROJ_QKV_C) or tuple(w_qkv.shape) != (PROJ_QKV_N, PROJ_QKV_C):
+        raise ValueError(f"sd_amd.proj_qkv_pack: unsupported shapes {tuple(w_in.shape)} / {tuple(w_qkv.shape)}")
+    perm = proj_qkv_perm().to(w_in.device)
+    b_in = torch.zeros(PROJ_QKV_C, device=w_in.device) if b_in is None else b_in.detach().float()
+    b_qkv = torch.zeros(PROJ_QKV_N, device=w_in.device) if b_qkv is None else b_qkv.detach().float().to(w_in.device)
+    return torch.cat([w_in[perm], w_qkv.to(w_in.device)], 0), torch.cat([b_in[perm], b_qkv], 0)
+
+
+def proj_qkv_unpack(w, b):
+    """Inverse of ``proj_qkv_pack``: (w_in, b_in, w_qkv, b_qkv)."""
+    perm = proj_qkv_perm().to(w.device)
+    w_in, b_in = torch.empty_like(w[:PROJ_QKV_C]), torch.empty_like(b[:PROJ_QKV_C])
+    w_in[perm], b_in[perm] = w[:PROJ_QKV_C], b[:PROJ_QKV_C]
+    return w_in, b_in, w[PROJ_QKV_C:], b[PROJ_QKV_C:]
+
+
+def proj_norm_qkv_supported(in_features, features, qkv_features):
+    return bool(lib().sdk_proj_norm_qkv_supported(in_features, features, qkv_features))
+
+
+_CU_COUNT = {}
+
+
+def cu_count(dev):
+    """Compute units of a device (cached: asked on every routed call)."""
+    key = torch.device(dev)
+    if key not in _CU_COUNT:
+        _CU_COUNT[key] = torch.cuda.get_device_properties(key).multi_processor_count
+    return _CU_COUNT[key]
+
+
+def proj_qkv_chain_fills(rows, cus):
+    """The routing rule of the chained kernel, stated once: its 256-row panels must fill the CUs as the row-panel
+    kernel's do — one round (``ceil(rows / 256) <= cus``) or a last round that is at least half full.  C5's 96x96
+    level (288 panels on 256 CUs: a second round of 32) is where the plain row-panel kernel already loses."""
+    panels = (rows + PROJ_QKV_PANEL - 1) // PROJ_QKV_PANEL
+    last = panels % cus
+    return panels <= cus or last == 0 or 2 * last >= cus
+
+
+class PackedProjQkv:
+    """proj_in (320 -> 320, bias) and the self-attention's concatenated to_q | to_k | to_v (320 -> 960) packed for
+    ``proj_norm_qkv``: one fp16 [1280][320] matrix and one fp32 [1280] bias (``proj_qkv_pack``)."""
+
+    def __init__(self, w_in, b_in, w_qkv, device, b_qkv=None):
+        w, b = proj_qkv_pack(w_in, b_in, w_qkv, b_qkv)
+        self.w = w.to(device=device, dtype=torch.float16).contiguous()
+        self.b = b.to(device=device, dtype=torch.float32).contiguous()
+
+
+def proj_norm_qkv(pk: PackedProjQkv, x, norm, gn=None, hw=None, tok=None, qkv=None):
+    """``(tok, qkv)`` with tok = proj_in(xn) and qkv = [q | k | v](LayerNorm(tok)) in one launch; xn = x ([M, 320] fp16
+    rows), or with ``gn=(scale, shift)`` (fp32 [M / hw, 320], ``group_norm_affine``) and ``hw`` rows per image the
+    GroupNorm of x applied on the way in.  ``norm=(gamma, beta, eps)`` of the LayerNorm (fp32 [320]).  The bits of
+    ``group_norm(silu=False)`` -> ``token_linear(norm=)`` -> ``linear`` on the q|k|v weight."""
+    _need_cuda(x, "proj_norm_qkv x")
+    M, K = x.shape
+    if K != PROJ_QKV_C or x.stride(-1) != 1:
+        raise ValueError("sd_amd.proj_norm_qkv: x must be [M, 320] with unit column stride")
+    g, bt, eps = norm
+    _need_cuda(g, "proj_norm_qkv gamma", torch.float32)
+    _need_cuda(bt, "proj_norm_qkv beta", torch.float32)
+    if g.numel() != PROJ_QKV_C or bt.numel() != PROJ_QKV_C:
+        raise ValueError("sd_amd.proj_norm_qkv: norm gamma / beta must have 320 elements")
+    if tok is None:
+        tok = torch.empty(M, PROJ_QKV_C, dtype=torch.float16, device=x.device)
+    if qkv is None:
+        qkv = torch.empty(M, PROJ_QKV_N, dtype=torch.float16, device=x.device)
+    _claim(tok)
+    _claim(qkv)
+    a = ProjNormQkvArgs()
+    a.x, a.w, a.bias, a.gamma, a.beta = x.data_ptr(), pk.w.data_ptr(), pk.b.data_ptr(), g.data_ptr(), bt.data_ptr()
+    a.tok, a.qkv = tok.data_ptr(), qkv.data_ptr()
+    a.x_ld, a.tok_ld, a.qkv_ld = x.stride(0), tok.stride(0), qkv.stride(0)
+    a.rows, a.in_features, a.features, a.qkv_features = M, K, tok.shape[1], qkv.shape[1]
+    a.eps = float(eps)
+    if gn is not None:
+        sc, sh = gn
+        _need_cuda(sc, "proj_norm_qkv gn scale", torch.float32)
+        _need_cuda(sh, "proj_norm_qkv gn shift", torch.float32)
+        if hw and (not sc.is_contiguous() or not sh.is_contiguous() or sc.numel() != M // hw * PROJ_QKV_C
+                   or sh.numel() != sc.numel()):
+            raise ValueError("sd_amd.proj_norm_qkv: gn scale / shift must be contiguous fp32 [M / hw, 320]")
+        a.gn_scale, a.gn_shift = sc.data_ptr(), sh.data_ptr()
+    a.hw = int(hw or 0)
+    if PROFILER.active:
+        # x in, tok and qkv out: the GroupNorm output and norm1(tok) never cross HBM
+        PROFILER.begin("proj_norm_qkv", None, shape=(M, PROJ_QKV_C + PROJ_QKV_N, K),
+                       nbytes=2 * M * (K + PROJ_QKV_C + PROJ_QKV_N))
+        PROFILER._cur = PROFILER._cur[:2] + (2.0 * M * K * (PROJ_QKV_C + PROJ_QKV_N),) + PROFILER._cur[3:]
+    check(lib().sdk_proj_norm_qkv(C.byref(a), _stream()), "proj_norm_qkv")
+    if PROFILER.active:
+        PROFILER.end()
+    return tok, qkv
 
 
 # --------------------------------------------------------------------------- sampler glue

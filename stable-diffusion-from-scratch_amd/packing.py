@@ -81,6 +81,12 @@ def gn_affine(gn, x):
     return ops.group_norm_affine(x, gn._g, gn._b, gn.eps, gn.num_groups)
 
 
+def gn_scale_shift(gn, x):
+    """The same affine from the statistics x's producing convs emitted (else a statistics pass): what ``gn_norm``
+    applies, for a consumer that applies it itself."""
+    return ops.group_norm_scale_shift(x, gn._g, gn._b, gn.eps, gn.num_groups)
+
+
 def gn_norm(gn, x, silu=True, pad=0):
     """GroupNorm (+ SiLU) of x materialised, zero-bordered by ``pad`` — one ``sdk_group_norm``."""
     return ops.group_norm(x, gn._g, gn._b, gn.eps, gn.num_groups, silu=silu, pad=pad)
